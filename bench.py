@@ -10,20 +10,25 @@ shape (one-subgraph-per-GPU data parallelism, weak scaling) and the parameter
 gradients are averaged with one RCCL all-reduce per step inside the timed
 region (experiments/cora_benchmark_graphsaint_distributed.py:63-94 as intended).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg4|cfg3|cfg3-L1|cfg3-L4|cfg5|cora|ampgcn-default|cfg4-saint|tiny] [--dtype f32|bf16] [--gemm native|fp32|bf16x3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg4|cfg3|cfg3-L1|cfg3-L4|cfg5|cora|ampgcn-default|cfg4-saint|tiny] [--dtype f32|bf16] [--gemm native|fp32|bf16x3] [--full] [--dump-outputs DIR]
 
-Prints ONE JSON line on rank 0.  `roofline` prices the dominant kernel against
-the 8 TB/s HBM3E spec peak with durations measured live by HIP events on the
-launch stream over the timed region; `cpu_baseline` is the reference-shaped CPU
-restatement (oracle/ampconv_torch.py) timed on the host cores on a bounded
-sub-sample of the same workload (rank 0, N=1 only).  Beside the headline the line
-carries: `saint` (every N: BASELINE config 4 as written -- the resident graph, one
-GraphSAINT subgraph per rank per step -- measured on the same ranks right after
-the full-graph pass), `extra_workloads` (N = 1: configs 3 and 5, the L = 1 / L = 4
-sweeps of config 3, the Cora-sized config 1/2 shape and the reference's class-default
-layer shape, a few steps each), `alt_gemm` (the same step on the library's fp32 GEMMs),
-`dist` (backend, world size and the number of ranks an all-reduce of ones saw) and
-per-rank kernel and all-reduce times, so that one line diagnoses a scaling run.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and
+reports them: `value`, `ms_per_step` (wall clock of one timed step), and the figures
+taken from those same steps -- `roofline` prices the dominant kernel against the
+8 TB/s HBM3E spec peak with durations measured live by HIP events on the launch
+stream, per-rank kernel and all-reduce times, `dist` (backend, world size and the
+number of ranks an all-reduce of ones saw).  --dump-outputs DIR writes what the last
+timed step computed (y, x.grad, the parameter gradients; see _outputs) as .npy files.
+
+--full adds the side measurements, each run after the headline's steps:
+`cpu_baseline` (the reference-shaped CPU restatement, oracle/ampconv_torch.py, timed
+on the host cores on a bounded sub-sample of the same workload; rank 0, N=1 only),
+`saint` (every N: BASELINE config 4 as written -- the resident graph, one GraphSAINT
+subgraph per rank per step -- measured on the same ranks right after the full-graph
+pass), `extra_workloads` (N = 1: configs 3 and 5, the L = 1 / L = 4 sweeps of
+config 3, the Cora-sized config 1/2 shape and the reference's class-default layer
+shape, a few steps each) and `alt_gemm` (the same step on the library's fp32 GEMMs),
+so that one line diagnoses a scaling run.
 """
 import argparse
 import json
@@ -138,6 +143,25 @@ def make_batch(N, E, L, D, seed, dev, dtype=torch.float32, rmat=False):
     return x, ei, dy
 
 
+DUMP_LIMIT_BYTES = 48 << 20          # --dump-outputs: the arrays of one run together (headroom below 64 MB)
+
+
+def _outputs(y, x, params, extra=None):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the layer output `y`, `x.grad` and
+    the parameter gradients under their torch names (`<parameter>.grad`), plus `extra` -- as float32 numpy arrays
+    (`extra`: as given).  y and x.grad are cut to one fixed, seeded sample of rows (the same rows on every run; every
+    row when they fit) so that all arrays together stay within DUMP_LIMIT_BYTES."""
+    out = dict(extra or {})
+    out.update({n + '.grad': p.grad.detach().float().cpu().numpy() for n, p in params if p.grad is not None})
+    left = DUMP_LIMIT_BYTES - sum(a.nbytes for a in out.values())
+    n = y.size(0)
+    rows = min(n, left // (4 * (y[0].numel() + x[0].numel())))
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:rows].sort().values.to(y.device)
+    out['y'] = y.detach().index_select(0, idx).float().cpu().numpy()
+    out['x.grad'] = x.grad.index_select(0, idx).float().cpu().numpy()
+    return out
+
+
 def host_cores():
     """CPU threads this process may really use: affinity mask, capped by the cgroup CPU quota."""
     n = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
@@ -213,11 +237,17 @@ def parse_args():
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--workload', default=os.environ.get('AMPCONV_BENCH_WORKLOAD', 'cfg4'))
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, the side measurements too: CPU baseline, library-GEMM pass, GraphSAINT '
+                         'batches, extra workloads (the --no-* options below leave single ones out)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, node ids float64; rows of large outputs: "
+                         "a fixed seeded sample, at most 48 MiB in all)")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
     ap.add_argument('--no-alt-gemm', action='store_true',
-                    help='skip the extra pass with the projections on the library GEMMs (profiling runs)')
+                    help='--full without the extra pass with the projections on the library GEMMs (profiling runs)')
     ap.add_argument('--no-extra', action='store_true',
-                    help='skip the side measurements of the default run (N = 1: configs 3 and 5; N > 1: GraphSAINT batches)')
+                    help='--full without the side workloads (N = 1: configs 3 and 5; every N: GraphSAINT batches)')
     ap.add_argument('--softmax-free', action='store_true',
                     help="the reference's softmax-free attention variant (AMPConv(..., softmax=False)); not the headline")
     ap.add_argument('--dtype', default=None, choices=['f32', 'bf16'],
@@ -228,7 +258,10 @@ def parse_args():
                          "cores -- six bf16 ones for small operands --, error below the fp32 library GEMM's "
                          "-- csrc/proj_gemm.hip), 'fp32' (library GEMMs, rocBLAS) or 'bf16x3' (hipBLASLt's "
                          "3-product split, 8x the error; ampnet_amd.conv.functional.gemm_precision)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 def launch_ranks(n):
@@ -340,12 +373,13 @@ def make_layer(D, H, tdt, dev, args, dist_on, softmax=True):
     return layer, GradientAllReducer(layer.parameters())
 
 
-def measure_saint(workload, steps, warmup, args, rank, world, dev, dist_on, dt_name):
+def measure_saint(workload, steps, warmup, args, rank, world, dev, dist_on, dt_name, outputs=None):
     """GraphSAINT-batch mode (BASELINE config 4 as written; experiments/cora_benchmark_graphsaint_distributed.py:64-94):
     per rank per step GraphSAINTRandomWalkSampler.sample() -> row gather of the resident features -> AMPConv forward +
     backward on the induced subgraph -> gradient all-reduce.  Returns (on every rank) the measurement as a dict:
     `value` = sampled edges processed by all ranks per second; the sampler's and the all-reduce's share of the step,
-    the host read-backs, per-rank kernel times."""
+    the host read-backs, per-rank kernel times.  `outputs` (a dict): filled with _outputs() of the last timed step, the
+    sampled node ids included."""
     import types
     from ampnet_amd import GraphSAINTRandomWalkSampler, graph_cache, _lib
     from ampnet_amd.sampler import gather_rows
@@ -388,6 +422,7 @@ def measure_saint(workload, steps, warmup, args, rank, world, dev, dist_on, dt_n
         if timed:
             ev.append((e0, e1))
             sizes.append((int(node_idx.numel()), int(ei_sub.size(1))))
+        return y, xs, node_idx
 
     try:
         for _ in range(warmup):
@@ -396,12 +431,17 @@ def measure_saint(workload, steps, warmup, args, rank, world, dev, dist_on, dt_n
         timer.enabled = True
         t0 = time.perf_counter()
         for _ in range(steps):
-            step(True)
+            last = None                                           # no step's results are held across the next step
+            last = step(True)
         _fence(dist_on)
         dt = time.perf_counter() - t0
     finally:
         timer.enabled = False
         _lib.load = orig_load
+    if outputs is not None:
+        y, xs, node_idx = last
+        outputs.update(_outputs(y, xs, layer.named_parameters(), {'node_idx': node_idx.cpu().numpy().astype('float64')}))
+    last = None
     tot = torch.tensor([dt, float(sum(e for _, e in sizes)), float(sum(n for n, _ in sizes))], dtype=torch.float64,
                        device=dev)
     if dist_on:
@@ -451,9 +491,10 @@ def measure_saint(workload, steps, warmup, args, rank, world, dev, dist_on, dt_n
     }
 
 
-def measure_full(workload, steps, warmup, args, rank, world, dev, dist_on, dt_name, alt=False):
+def measure_full(workload, steps, warmup, args, rank, world, dev, dist_on, dt_name, alt=False, outputs=None):
     """One graph of the workload's shape per rank; a step = CSR/CSC build + one AMPConv layer forward + backward
-    (+ the gradient all-reduce when a process group is up).  Returns the measurement as a dict (on every rank)."""
+    (+ the gradient all-reduce when a process group is up).  Returns the measurement as a dict (on every rank).
+    `outputs` (a dict): filled with _outputs() of the last timed step."""
     from ampnet_amd import graph_cache, _lib
     N, E, L, D, H, desc = WORKLOADS[workload]
     tdt = torch.bfloat16 if dt_name == 'bf16' else torch.float32
@@ -481,6 +522,7 @@ def measure_full(workload, steps, warmup, args, rank, world, dev, dist_on, dt_na
             a1.record()
             if timed:
                 ar_ev.append((a0, a1))
+        return y
 
     try:
         for _ in range(warmup):
@@ -490,14 +532,18 @@ def measure_full(workload, steps, warmup, args, rank, world, dev, dist_on, dt_na
         step_events = []
         t0 = time.perf_counter()
         for _ in range(steps):
+            y = None                                          # no step's output is held across the next step
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            step(True)
+            y = step(True)
             e1.record()
             step_events.append((e0, e1))
         _fence(dist_on)
         dt = time.perf_counter() - t0
         timer.enabled = False
+        if outputs is not None:
+            outputs.update(_outputs(y, x, layer.named_parameters()))
+        y = None
         step_ms = sorted(a.elapsed_time(b) for a, b in step_events)
         median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -759,13 +805,16 @@ def main():
             torch.cuda.synchronize()
 
     dt_name = args.dtype or ('bf16' if args.workload == 'cfg5' else 'f32')
+    outputs = {} if args.dump_outputs and rank == 0 else None
     if args.workload in SAINT:
-        out = measure_saint(args.workload, args.steps, args.warmup, args, rank, world, dev, dist_on, dt_name)
+        out = measure_saint(args.workload, args.steps, args.warmup, args, rank, world, dev, dist_on, dt_name,
+                            outputs=outputs)
     else:
-        alt = (world == 1 and dt_name == 'f32' and args.gemm == 'native' and not args.no_alt_gemm
+        alt = (args.full and world == 1 and dt_name == 'f32' and args.gemm == 'native' and not args.no_alt_gemm
                and not args.softmax_free)
-        out = measure_full(args.workload, args.steps, args.warmup, args, rank, world, dev, dist_on, dt_name, alt=alt)
-        side = not args.no_extra and not args.softmax_free and args.dtype is None
+        out = measure_full(args.workload, args.steps, args.warmup, args, rank, world, dev, dist_on, dt_name, alt=alt,
+                           outputs=outputs)
+        side = args.full and not args.no_extra and not args.softmax_free and args.dtype is None
         saint_of = {'cfg4': 'cfg4-saint', 'tiny': 'tiny-saint'}
         if side and args.workload in saint_of:
             # BASELINE config 4 as written, on the same ranks (every N, one rank included): the mode whose scaling curve
@@ -786,7 +835,7 @@ def main():
                 for w, k in extra}
             # the same Cora-sized layer on a FIXED graph, its launches recorded and replayed (HIP graphs)
             out['extra_workloads']['cora-graphed'] = measure_graphed('cora', 200 if args.workload == 'cfg4' else 5, 5, args, dev)
-        if world == 1 and not args.no_cpu_baseline and not args.softmax_free and rank == 0:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.softmax_free and rank == 0:
             N, E, L, D, H, _ = WORKLOADS[args.workload]
             out['cpu_baseline'] = cpu_baseline(L, D, H, E / N)
     if dist_on:
@@ -795,6 +844,11 @@ def main():
         dist.all_reduce(seen)
         out['dist'] = {'backend': dist.get_backend(), 'world_size': dist.get_world_size(),
                        'ranks_seen': int(seen.item())}
+    if outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + '.npy'), a)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if dist_on:

@@ -139,6 +139,28 @@ def test_bench_node_phase_roofline_object(monkeypatch):
     assert bench._node_phase_mfma(flops, 0.0, 'f32', 'native') is None
 
 
+
+def test_bench_dumped_outputs_are_a_fixed_row_sample(monkeypatch):
+    """bench.py --dump-outputs: y and x.grad are cut to the SAME fixed, seeded rows (all rows, in order, when they fit),
+    float32, and everything together stays within the size limit; the parameter gradients are whole."""
+    import bench
+    import numpy as np
+    layer = torch.nn.Linear(64, 32)
+    x = torch.randn(1000, 64, requires_grad=True)
+    y = layer(x)
+    y.backward(torch.randn_like(y))
+    params = list(layer.named_parameters())
+    full = bench._outputs(y, x, params)
+    assert np.array_equal(full['y'], y.detach().numpy()) and np.array_equal(full['x.grad'], x.grad.numpy())
+    assert np.array_equal(full['weight.grad'], layer.weight.grad.numpy()) and full['bias.grad'].shape == (32,)
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 64 << 10)
+    a, b = bench._outputs(y, x, params), bench._outputs(y, x, params, {'node_idx': np.arange(10.0)})
+    assert sum(v.nbytes for v in a.values()) <= 64 << 10 and sum(v.nbytes for v in b.values()) <= 64 << 10
+    assert all(v.dtype == np.float32 for v in a.values()) and b['node_idx'].dtype == np.float64
+    rows = [int(np.nonzero((y.detach().numpy() == r).all(axis=1))[0][0]) for r in a['y']]
+    assert 0 < len(rows) < 1000 and rows == sorted(set(rows))
+    assert np.array_equal(a['x.grad'], x.grad.numpy()[rows]) and np.array_equal(bench._outputs(y, x, params)['y'], a['y'])
+
 def test_register_budgets_of_the_kernels_that_must_not_spill():
     """hipcc's kernel-resource-usage remarks, kept by __graft_entry__.build() in build/obj/*.usage.json.
     * proj_rows_kernel streams its rows with inline-assembly loads whose waits are counted by hand: a register spilled

@@ -896,7 +896,7 @@ def test_gemm_precision_is_restored(dev):
 
 
 def test_bench_launches_two_ranks(dev):
-    """`python bench.py --gpus 2` starts its two ranks itself and reports n_gpus = 2 (gloo here: both ranks
+    """`python bench.py --gpus 2 --full` starts its two ranks itself and reports n_gpus = 2 (gloo here: both ranks
     share the one card of the test box; on the 8-GPU node the same path runs over RCCL)."""
     import json
     import subprocess
@@ -906,8 +906,8 @@ def test_bench_launches_two_ranks(dev):
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--workload', 'tiny',
-                        '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-alt-gemm'], env=env, timeout=600,
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+                        '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-alt-gemm'], env=env,
+                       timeout=600, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, r.stdout
@@ -974,7 +974,7 @@ def test_rmat_graph_with_id_structured_degrees(dtype, dev):
 def test_bench_rccl_path_single_rank(dev):
     """The N-rank run's RCCL code path (nccl process group with device_id, parameter broadcast, gradient all-reduce,
     barriers, MAX reduction of the time) executed by ONE rank on the one GPU of the test box -- two ranks cannot share
-    a card under RCCL, so this is as much of the `--gpus N` path as a single GPU can run."""
+    a card under RCCL, so this is as much of the `--gpus N --full` path as a single GPU can run."""
     import json
     import subprocess
     import sys
@@ -984,7 +984,7 @@ def test_bench_rccl_path_single_rank(dev):
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT'):      # bench.py picks a free port itself
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'tiny', '--steps', '2', '--warmup', '1',
-                        '--no-cpu-baseline', '--no-alt-gemm'], env=env, timeout=600, stdout=subprocess.PIPE,
+                        '--full', '--no-cpu-baseline', '--no-alt-gemm'], env=env, timeout=600, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][0])
@@ -997,8 +997,8 @@ def test_bench_rccl_path_single_rank(dev):
 
 
 def test_bench_default_line_carries_saint_and_extras_without_a_process_group(dev):
-    """the plain N = 1 run (no process group) measures the GraphSAINT-batch mode and the extra
-    workloads too; stdout stays ONE JSON line."""
+    """the N = 1 run with --full (no process group) measures the GraphSAINT-batch mode and the
+    extra workloads too; stdout stays ONE JSON line."""
     import json
     import subprocess
     import sys
@@ -1007,7 +1007,7 @@ def test_bench_default_line_carries_saint_and_extras_without_a_process_group(dev
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'AMPCONV_BENCH_FORCE_DIST'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'tiny', '--steps', '2', '--warmup', '1',
-                        '--no-cpu-baseline', '--no-alt-gemm'], env=env, timeout=600, stdout=subprocess.PIPE,
+                        '--full', '--no-cpu-baseline', '--no-alt-gemm'], env=env, timeout=600, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -1017,6 +1017,42 @@ def test_bench_default_line_carries_saint_and_extras_without_a_process_group(dev
     assert out['saint']['steps'] >= 20 and out['saint']['value'] > 0 and out['saint']['allreduce_ms'] == 0
     assert out['extra_workloads']['cora']['ms_per_step'] > 0
 
+
+
+def test_bench_plain_line_is_lean_and_dumps_outputs(dev, tmp_path):
+    """A plain run (no --full) times exactly --steps steps and carries none of the side measurements; --dump-outputs
+    writes y, x.grad and the parameter gradients of the last timed step, and two runs with the same arguments write
+    the same arrays (same seeded inputs, same sampled rows)."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    env = dict(os.environ)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'AMPCONV_BENCH_FORCE_DIST'):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f'run{run}'
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'tiny', '--steps', '3',
+                            '--warmup', '1', '--dump-outputs', str(d)], env=env, timeout=600, stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, text=True)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out['steps'] == 3 and out['warmup'] == 1 and out['ms_per_step'] > 0 and out['value'] > 0
+        assert out['unit'] == 'edges/s' and out['higher_is_better'] is True and out['dtype'] == 'f32'
+        assert not {'saint', 'extra_workloads', 'cpu_baseline', 'alt_gemm'} & set(out)
+        arrays = {f.name[:-4]: np.load(f) for f in d.iterdir()}
+        assert {'y', 'x.grad', 'multi_head_attention.in_proj_weight.grad', 'multi_head_attention.in_proj_bias.grad',
+                'multi_head_attention.out_proj.weight.grad', 'multi_head_attention.out_proj.bias.grad'} <= set(arrays)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+        assert arrays['y'].shape[1] == 20 * 256 and arrays['x.grad'].shape == arrays['y'].shape
+        assert np.abs(arrays['y']).max() > 0 and np.abs(arrays['x.grad']).max() > 0
+        dumps.append(arrays)
+    for k, a in dumps[0].items():
+        np.testing.assert_allclose(dumps[1][k], a, rtol=1e-5, atol=1e-6, err_msg=k)
 
 def test_nt4_kernels_match_round1_tiling(dev, tmp_path):
     """The 4x4x1 tail kernels (default) against the same build with AMPCONV_{FWD,DST,SRC}_NT4=0 (every product on
