@@ -15,6 +15,7 @@ Data layout in HBM (fp32):
 """
 import contextlib
 import ctypes
+import dataclasses
 import os
 import threading
 
@@ -188,20 +189,6 @@ def proj_rows_planes(a2, image, bound, bias=None, rowptr=None, L=0, row_scale=0,
 PLANES_MIN_L = 5
 
 
-def planes_ok(L, D, H, shared):
-    """Does the plane-format edge phase serve this layer call?  (Only with the scaled projections; the caller checks.)"""
-    return bool(EDGE_PLANES and shared and D % 128 == 0 and L >= PLANES_MIN_L
-                and _lib.load().ampconv_planes_supported(L, D, H))
-
-
-def scaled_views_ok(L, D, H, shared):
-    """Do the bound-carrying fp32 entry points (include/ampconv.h, ampconv_*_edge_scaled: the workgroup-per-unit shapes --
-    L <= 64, even head widths up to 64 outside the one-wave-per-unit kernels' L <= 20 x {16, 32} -- e.g. the AMPGCN class
-    defaults L = 40, D = 100, H = 2) serve this layer call?  Only with the scaled projections and
-    the statistics hand-off; the caller checks the former."""
-    return bool(EDGE_PLANES and SOFTMAX_STATS and shared and L >= PLANES_MIN_L and _lib.load().ampconv_scaled_supported(L, D, H))
-
-
 def absmax(t2, out=None, reset=False):
     """Largest finite magnitude of a 2-D tensor with contiguous rows, as a one-element device tensor (no host sync):
     the scale source of the fp32 projections' two-plane mode.  `out`: merge into an existing maximum (reset: zero it
@@ -318,21 +305,180 @@ def _zero_unlisted(t2, nodes, n_nodes, L):
                'ampconv_mask_rows')
 
 
-def node_lists(csr, dtype, L, native, shared):
-    """The graph's node lists when this call can use them: bf16 projections of a self-attention layer (xq is xkv) with
-    16 <= L <= 128 on a graph where a good share of the nodes has no edge (EdgeCSR.active_nodes), else None."""
-    if not (NODE_LISTS and native and shared and dtype == torch.bfloat16 and 16 <= L <= 128):
-        return None
-    return csr.active_nodes()
-
-
 def edge_forward(Q, K, V, csr, n_rows, L, D, H, out2d, qidx=None, dtype=_lib.AMPCONV_F32):
+    """The plain forward edge pass (ampconv_fwd_edge): what edge_fwd runs for a 'plain' plan."""
     lib = _lib.load()
     plan, nch, ws = csr.hub_args('dst', L, D, 1) if qidx is None else (None, 0, None)
     rc = lib.ampconv_fwd_edge(Q, K, V, csr.rowptr.data_ptr(), csr.col.data_ptr(), _ptr(qidx),
                               n_rows, L, D, H, _view(out2d, 0, L, D // H), plan, nch, _ptr(ws),
                               dtype, _stream())
     _lib.check(rc, 'ampconv_fwd_edge')
+
+
+@dataclasses.dataclass(frozen=True)
+class LayerPlan:
+    """Which kernels one AMPConvFunction call runs: chosen once by choose_plan, kept on ctx, and turned into the backward
+    pass's plan by backward().
+      native      the projections run on libampconv's own kernels (proj_* above); False: library GEMMs (`gemm`)
+      scaled      fp32 projections in the scaled two-plane mode (their operand maxima: Scalars); False: exact
+      edge        'planes': Q|K|V and dObar in the plane format, ampconv_*_edge_planes; 'views': fp32 views with bounds,
+                  ampconv_*_edge_scaled; 'plain': ampconv_fwd_edge / _bwd_edge_dst / _bwd_edge_src at storage `dtype`
+      lists       EdgeCSR.active_nodes() when the projections run over the listed nodes only (bf16), else None
+      qkv_to_f32  (backward plans) the saved qkv is in the plane format but this pass reads fp32: planes_to_f32 first"""
+    L: int
+    D: int
+    H: int
+    shared: bool = True
+    native: bool = False
+    scaled: bool = False
+    edge: str = 'plain'
+    dtype: int = _lib.AMPCONV_F32
+    gemm: str = 'fp32'
+    lists: object = None
+    qkv_to_f32: bool = False
+
+    @property
+    def dh(self):
+        return self.D // self.H
+
+    def backward(self, dy_narrow):
+        """The backward pass's plan.  The scaled products serve dY only if it lies within 2^RANGE_LOG2 of its maximum too
+        (dy_narrow, operand_stats); otherwise the whole pass takes the exact kernels: six-product projections and plain
+        fp32 edge passes."""
+        if not self.scaled or dy_narrow:
+            return self
+        return dataclasses.replace(self, scaled=False, edge='plain', qkv_to_f32=self.edge == 'planes')
+
+
+def choose_plan(L, D, H, shared, dtype, gemm, numel, x_narrow, xkv_narrow, active_nodes, capturing,
+                edge_dtype=_lib.AMPCONV_F32):
+    """The LayerPlan of one call.  dtype: storage (torch); numel: elements of x (query side).  What depends on data comes
+    in as callables, called only once the cheap conditions hold, x first: x_narrow / xkv_narrow -> operand_stats' verdict
+    on x / xkv (xkv: unshared calls; one pass and one read-back unless cached, so never while a HIP graph is being
+    recorded: `capturing`), active_nodes -> EdgeCSR.active_nodes(), or None when the call's rows are not the graph's
+    nodes.  edge_dtype: storage code of the plain edge passes (bf16 storage: always AMPCONV_BF16)."""
+    lib = _lib.load()
+    bf16 = dtype == torch.bfloat16
+    native = proj_native(gemm, dtype, D)
+    # node lists: bf16 projections of a self-attention layer with 16 <= L <= 128 on a graph where a good share of the
+    # nodes has no edge
+    lists = None
+    if NODE_LISTS and native and shared and bf16 and 16 <= L <= 128 and active_nodes is not None:
+        lists = active_nodes()
+    # the scaled mode serves operands that lie within 2^RANGE_LOG2 of their maximum; anything wider takes the exact
+    # six-product kernels
+    scaled = bool(native and PROJ_SCALED and dtype == torch.float32 and numel >= PROJ_SCALED_MIN_ELEMENTS
+                  and not capturing() and x_narrow() and (shared or xkv_narrow()))
+    edge = 'plain'
+    if scaled and EDGE_PLANES and shared and L >= PLANES_MIN_L:
+        if D % 128 == 0 and lib.ampconv_planes_supported(L, D, H):
+            edge = 'planes'
+        elif SOFTMAX_STATS and lib.ampconv_scaled_supported(L, D, H):   # (the workgroup-per-unit shapes, e.g. the
+            edge = 'views'                                              # AMPGCN class defaults L = 40, D = 100, H = 2)
+    return LayerPlan(L, D, H, shared, native, scaled, edge, _lib.AMPCONV_BF16 if bf16 else edge_dtype, gemm, lists)
+
+
+@dataclasses.dataclass
+class Scalars:
+    """The device scalars of one layer call (one-element fp32 tensors; None where a field does not apply, i.e. all of
+    them unless the plan is scaled): operand maxima of the scaled projections, and `bounds`, the float[4] that the plane
+    and bound-carrying entry points read (include/ampconv.h), under the names below."""
+    x: torch.Tensor = None          # max |x| (query side; self-attention: all of x), operand_stats
+    xkv: torch.Tensor = None        # max |xkv| (unshared calls), operand_stats
+    obar: torch.Tensor = None       # operand maximum of Obar, recorded by the in-projection (for_forward)
+    bounds: torch.Tensor = None     # float[4] of the 'planes' and 'views' plans
+    dy: torch.Tensor = None         # max |dY|, operand_stats
+    dqkv: torch.Tensor = None       # max |dQ| (self-attention: of all of dQKV), recorded by the passes that write it
+    dkv: torch.Tensor = None        # max |dK | dV| (unshared calls)
+
+    qkv_bound = property(lambda s: s.bounds[0:1])       # >= max |Q|K|V|: the scale of the planes / views of QKV
+    dobar_bound = property(lambda s: s.bounds[1:2])     # >= max |dObar|: the scale of dObar's planes / views
+    v_max = property(lambda s: s.bounds[2:3])           # recorded max |V|
+    dobar_max = property(lambda s: s.bounds[3:4])       # recorded max |dObar|
+
+    @classmethod
+    def for_forward(cls, plan, x, xkv):
+        """Obar is a mean of convex combinations of V rows, so a maximum of |V| is its operand maximum, and the
+        in-projection records it into `obar`, which is: 'planes': v_max (the V third only); 'views': qkv_bound
+        (max |Q|K|V|, the scale of the whole tensor and the bound of |V|; the forward pass copies it to v_max, and the
+        backward pass likewise copies dobar_bound, the recorded max |dObar|, to dobar_max); 'plain': a scalar of its
+        own."""
+        if not plan.scaled:
+            return cls()
+        s = cls(x=x, xkv=xkv)
+        if plan.edge != 'plain':
+            s.bounds = torch.zeros(4, dtype=torch.float32, device=x.device)
+        s.obar = (s.v_max if plan.edge == 'planes' else s.qkv_bound if plan.edge == 'views'
+                  else torch.zeros(1, dtype=torch.float32, device=x.device))
+        return s
+
+    def for_backward(self, dy):
+        """The backward pass's holder: these scalars, max |dY| and a zeroed maximum of dQKV."""
+        return dataclasses.replace(self, dy=dy, dqkv=torch.zeros(1, dtype=torch.float32, device=dy.device))
+
+
+def _verdict(t2, key, maxima, name):
+    """choose_plan's callable for one operand: operand_stats' narrow-range verdict, its maximum kept in maxima[name]."""
+    def narrow():
+        st, ok = operand_stats(t2, key=key)
+        maxima[name] = st[0:1]
+        return ok
+    return narrow
+
+
+def _qkv_views(q, kv, L, D, dh):
+    """Views of the Q, K, V column thirds: all three in q (kv None: self-attention), or Q in q and K | V in kv."""
+    src, off = (q, D) if kv is None else (kv, 0)
+    return _view(q, 0, L, dh), _view(src, off, L, dh), _view(src, off + D, L, dh)
+
+
+# ---- the three edge passes, each through the entry point of the plan's family (views: _view; sc: the call's Scalars)
+def edge_fwd(plan, csr, Q, K, V, n_rows, obar, sc):
+    if plan.edge == 'plain':
+        return edge_forward(Q, K, V, csr, n_rows, plan.L, plan.D, plan.H, obar, dtype=plan.dtype)
+    name = 'ampconv_fwd_edge_' + ('planes' if plan.edge == 'planes' else 'scaled')
+    hub, nch, ws = csr.hub_args('dst', plan.L, plan.D, 1)
+    _lib.check(getattr(_lib.load(), name)(Q, K, V, csr.rowptr.data_ptr(), csr.col.data_ptr(), n_rows, plan.L, plan.D,
+                                          plan.H, _view(obar, 0, plan.L, plan.dh), hub, nch, _ptr(ws),
+                                          sc.bounds.data_ptr(), _stream()), name)
+
+
+def edge_bwd_dst(plan, csr, Q, K, V, dO, n_rows, dQ, sc):
+    """dQ; returns the softmax statistics (normaliser, delta) per edge that this pass hands to the source pass, saving it
+    its cross-lane reductions (include/ampconv.h), or None: that pass reduces its own.  Records max |dQ| into sc.dqkv."""
+    lib = _lib.load()
+    L, D, H = plan.L, plan.D, plan.H
+    stats = spos = None
+    nstat = lib.ampconv_softmax_stats_bytes(csr.num_edges, L, D, H, plan.dtype) if SOFTMAX_STATS else 0
+    if nstat:
+        stats = torch.empty(nstat // 4, dtype=torch.float32, device=csr.rowptr.device)
+        spos = csr.csc_positions()
+    hub, nch, ws = csr.hub_args('dst', L, D, 1)
+    args = (Q, K, V, dO, csr.rowptr.data_ptr(), csr.col.data_ptr(), n_rows, L, D, H, dQ, hub, nch, _ptr(ws))
+    if plan.edge == 'plain':
+        name, args = 'ampconv_bwd_edge_dst', args + (_ptr(spos), _ptr(stats), _ptr(sc.dqkv), plan.dtype)
+    else:
+        name = 'ampconv_bwd_edge_dst_' + ('planes' if plan.edge == 'planes' else 'scaled')
+        args += (sc.bounds.data_ptr(), _ptr(spos), _ptr(stats), sc.dqkv.data_ptr())
+    _lib.check(getattr(lib, name)(*args, _stream()), name)
+    return stats
+
+
+def edge_bwd_src(plan, csr, Q, K, V, dO, n_src, dK, dV, stats, sc):
+    """dK, dV from the destination pass's statistics (None: its own softmax).  The 'planes' and 'views' passes record
+    max |dK | dV| into sc.dqkv as well; the plain fp32 kernels have no register to spare for it (csrc/edge_mfma.hip)."""
+    lib = _lib.load()
+    L, D, H = plan.L, plan.D, plan.H
+    hub, nch, ws = csr.hub_args('src', L, D, 2)
+    cinv = () if plan.edge == 'planes' else (csr.cinv.data_ptr(),)
+    args = (Q, K, V, dO, csr.cscptr.data_ptr(), csr.crow.data_ptr()) + cinv + (n_src, L, D, H, dK, dV, hub, nch,
+                                                                               _ptr(ws))
+    if plan.edge == 'plain':
+        name, args = 'ampconv_bwd_edge_src', args + (_ptr(stats), None, plan.dtype)
+    else:
+        name = 'ampconv_bwd_edge_src_' + ('planes' if plan.edge == 'planes' else 'scaled')
+        args += (sc.bounds.data_ptr(), _ptr(stats), sc.dqkv.data_ptr())
+    _lib.check(getattr(lib, name)(*args, _stream()), name)
 
 
 class AMPConvFunction(torch.autograd.Function):
@@ -355,7 +501,6 @@ class AMPConvFunction(torch.autograd.Function):
             raise ValueError(f'inputs are {xq.dtype} but the parameters are {w_in.dtype}: storage is all float32 or all '
                              f'bfloat16 (layer.to(torch.bfloat16))')
         if xq.dtype == torch.bfloat16:                   # bf16 storage: one mode only
-            dtype = _lib.AMPCONV_BF16
             if not ((dh in (16, 32) and L <= 20) or (dh % 2 == 0 and dh <= 64 and L <= 64)):
                 raise ValueError(f'bf16 storage is implemented for head dimensions 32 and 16 with at most 20 tokens per '
                                  f'node (csrc/edge_mfma_bf16.hip; BASELINE configs 5 and 3) and for even head dimensions '
@@ -363,82 +508,46 @@ class AMPConvFunction(torch.autograd.Function):
                                  f'got head dimension {dh}, {L} tokens: use float32 for this shape')
         Nq, Nk = xq.size(0), xkv.size(0)
         xq2 = xq.contiguous().view(Nq * L, D)
-        native = proj_native(gemm, xq.dtype, D)
-        imgs = None
         with torch.cuda.device(xq.device), gemm_precision(gemm):
-            if native:      # every weight image this call and its backward need, in one launch
+            xkv2 = xq2 if shared else xkv.contiguous().view(Nk * L, D)
+            maxima = {}
+            plan = choose_plan(L, D, H, shared, xq.dtype, gemm, xq2.numel(), _verdict(xq2, xq, maxima, 'x'),
+                               _verdict(xkv2, xkv, maxima, 'xkv'), csr.active_nodes if Nq == csr.num_nodes else None,
+                               torch.cuda.is_current_stream_capturing, dtype)
+            imgs = None
+            if plan.native:      # every weight image this call and its backward need, in one launch
                 ws = [w_in, w_out] if shared else [w_in[:D], w_in[D:], w_out]
                 imgs = proj_images([(w, False) for w in ws] + [(w, True) for w in ws])
-            lists = node_lists(csr, xq.dtype, L, native, shared and Nq == csr.num_nodes)
-            # fp32 storage: operand maxima for the scaled two-plane products, device-side.  am = [x (query side), the
-            # in-projection's output (K | V side: an upper bound of |Obar|, a mean of convex combinations of V rows),
-            # x (key/value side)]; inputs are measured by one pass, outputs recorded by the product that writes them
-            # The scaled mode serves operands that lie within 2^RANGE_LOG2 of their maximum (operand_stats: one pass, one
-            # 8-byte read-back, remembered per tensor version); anything wider takes the exact six-product kernels.
-            am = bounds = None
-            planes = scaledv = False
-            xkv2 = xq2 if shared else xkv.contiguous().view(Nk * L, D)
-            # (the read-back rules the mode out while a HIP graph is being recorded: ampnet_amd/graphed.py is for small graphs)
-            if (native and PROJ_SCALED and xq.dtype == torch.float32 and xq2.numel() >= PROJ_SCALED_MIN_ELEMENTS
-                    and not torch.cuda.is_current_stream_capturing()):
-                st, narrow = operand_stats(xq2, key=xq)
-                stk = None
-                if narrow and not shared:
-                    stk, narrow = operand_stats(xkv2, key=xkv)
-                if narrow:
-                    planes = planes_ok(L, D, H, shared)
-                    scaledv = not planes and scaled_views_ok(L, D, H, shared)
-                    # device scalars of the plane format (include/ampconv.h): [bound of Q|K|V, bound of dObar, recorded
-                    # max |V|, recorded max |dObar|]; max |V| doubles as the operand maximum of Obar (am[1]).
-                    # fp32 views with bounds (`scaledv`): the in-projection records max |Q|K|V| into bounds[0], which serves
-                    # as all of: the tensor's scale, the bound of |V|, and the operand maximum of Obar
-                    bounds = torch.zeros(4, dtype=torch.float32, device=xq.device) if planes or scaledv else None
-                    am = [st[0:1], bounds[2:3] if planes else bounds[0:1] if scaledv else
-                          torch.zeros(1, dtype=torch.float32, device=xq.device), None if shared else stk[0:1]]
-            sl = (lambda i: am[i]) if am is not None else (lambda i: None)
-            if planes:
+            sc = Scalars.for_forward(plan, maxima.get('x'), maxima.get('xkv'))
+            lists = plan.lists
+            kv = None
+            if plan.edge == 'planes':
                 # Q | K | V leave the in-projection as two fp16 planes scaled by a bound known before the product runs
-                # (max |x| times the largest absolute row sum of W, plus max |b|); the recorded maximum covers the V third
-                # only: it bounds Obar, a mean of convex combinations of V rows
-                proj_out_bound(w_in, False, b_in, am[0], bounds[0:1])
-                qkv = proj_rows_planes(xq2, imgs[0], bounds[0:1], b_in, amax=am[0], out_amax=am[1], amax_col0=2 * D, dh=dh)
-                Qv, Kv, Vv = (_view(qkv, i * D, L, dh) for i in range(3))
-                kv = None
+                # (max |x| times the largest absolute row sum of W, plus max |b|)
+                proj_out_bound(w_in, False, b_in, sc.x, sc.qkv_bound)
+                qkv = proj_rows_planes(xq2, imgs[0], sc.qkv_bound, b_in, amax=sc.x, out_amax=sc.obar, amax_col0=2 * D,
+                                       dh=dh)
             elif shared:
                 # (node lists: Q rows matter for nodes with in-edges, K / V rows for nodes with out-edges; the rows of
                 # nodes with neither are never read by an edge pass and stay unwritten)
-                qkv = (proj_rows(xq2, imgs[0], b_in, L=L, nodes=lists and lists['any'], amax=sl(0), out_amax=sl(1))
-                       if native else torch.addmm(b_in, xq2, w_in.t()))              # [N*L, 3D]
-                Qv, Kv, Vv = (_view(qkv, i * D, L, dh) for i in range(3))
-                kv = None
+                qkv = (proj_rows(xq2, imgs[0], b_in, L=L, nodes=lists and lists['any'], amax=sc.x, out_amax=sc.obar)
+                       if plan.native else torch.addmm(b_in, xq2, w_in.t()))              # [N*L, 3D]
+            elif plan.native:
+                qkv = proj_rows(xq2, imgs[0], b_in[:D], amax=sc.x)
+                kv = proj_rows(xkv2, imgs[1], b_in[D:], amax=sc.xkv, out_amax=sc.obar)
             else:
-                if native:
-                    qkv = proj_rows(xq2, imgs[0], b_in[:D], amax=sl(0))
-                    kv = proj_rows(xkv2, imgs[1], b_in[D:], amax=sl(2), out_amax=sl(1))
-                else:
-                    qkv = torch.addmm(b_in[:D], xq2, w_in[:D].t())         # [Nq*L, D]
-                    kv = torch.addmm(b_in[D:], xkv2, w_in[D:].t())         # [Nk*L, 2D]
-                Qv = _view(qkv, 0, L, dh)
-                Kv, Vv = _view(kv, 0, L, dh), _view(kv, D, L, dh)
+                qkv = torch.addmm(b_in[:D], xq2, w_in[:D].t())         # [Nq*L, D]
+                kv = torch.addmm(b_in[D:], xkv2, w_in[D:].t())         # [Nk*L, 2D]
+            Qv, Kv, Vv = _qkv_views(qkv, kv, L, D, dh)
             obar = torch.empty(Nq * L, D, dtype=xq.dtype, device=xq.device)
-            if planes:
-                plan, nch, ws = csr.hub_args('dst', L, D, 1)
-                _lib.check(lib.ampconv_fwd_edge_planes(Qv, Kv, Vv, csr.rowptr.data_ptr(), csr.col.data_ptr(), Nq, L, D, H,
-                                                       _view(obar, 0, L, dh), plan, nch, _ptr(ws), bounds.data_ptr(),
-                                                       _stream()), 'ampconv_fwd_edge_planes')
-            elif scaledv:
-                bounds[2:3].copy_(bounds[0:1])
-                plan, nch, ws = csr.hub_args('dst', L, D, 1)
-                _lib.check(lib.ampconv_fwd_edge_scaled(Qv, Kv, Vv, csr.rowptr.data_ptr(), csr.col.data_ptr(), Nq, L, D, H,
-                                                       _view(obar, 0, L, dh), plan, nch, _ptr(ws), bounds.data_ptr(),
-                                                       _stream()), 'ampconv_fwd_edge_scaled')
-            else:
-                edge_forward(Qv, Kv, Vv, csr, Nq, L, D, H, obar, dtype=dtype)
+            if plan.edge == 'views':
+                sc.v_max.copy_(sc.qkv_bound)                 # (Scalars.for_forward)
+            edge_fwd(plan, csr, Qv, Kv, Vv, Nq, obar, sc)
             if lists:       # the rows of the nodes with in-edges; the others are zeroed without being read
                 y = proj_rows(obar, imgs[1], b_out, L=L, nodes=lists['in'])
                 _zero_unlisted(y, lists['in'], Nq, L)
-            elif native:    # bias and the in-degree mask (rows nobody sends to stay exactly 0) in the epilogue
-                y = proj_rows(obar, imgs[1 if shared else 2], b_out, csr.rowptr, L, amax=sl(1))
+            elif plan.native:    # bias and the in-degree mask (rows nobody sends to stay exactly 0) in the epilogue
+                y = proj_rows(obar, imgs[1 if shared else 2], b_out, csr.rowptr, L, amax=sc.obar)
             else:
                 y = torch.addmm(b_out, obar, w_out.t())
                 io = _lib.AMPCONV_BF16 if y.dtype == torch.bfloat16 else _lib.AMPCONV_F32
@@ -446,15 +555,14 @@ class AMPConvFunction(torch.autograd.Function):
                 _lib.check(rc, 'ampconv_mask_rows')
         ctx.set_materialize_grads(False)     # no zero-filled [N*L, 3D] gradient for the qkv side output
         ctx.save_for_backward(xq2, xkv2, w_in, w_out, qkv, kv, obar)
-        ctx.csr, ctx.dims, ctx.shared, ctx.dtype, ctx.gemm = csr, (Nq, Nk, L, D, H), shared, dtype, gemm
-        ctx.lists, ctx.amax, ctx.bounds, ctx.plane_format = lists, am, bounds, planes
+        ctx.csr, ctx.dims, ctx.plan, ctx.scalars = csr, (Nq, Nk), plan, sc
         ctx.images_t = imgs[len(imgs) // 2:] if imgs else None     # the transposed images, for the input gradients
         ctx.mark_non_differentiable(qkv)
         if kv is not None:
             ctx.mark_non_differentiable(kv)
-        if planes:                          # plane format: the third output is what reads `qkv` back (planes_to_f32)
-            ctx.mark_non_differentiable(bounds)
-            return y.view(Nq, L * D), qkv, bounds
+        if plan.edge == 'planes':           # plane format: the third output is what reads `qkv` back (planes_to_f32)
+            ctx.mark_non_differentiable(sc.bounds)
+            return y.view(Nq, L * D), qkv, sc.bounds
         return y.view(Nq, L * D), qkv, kv
 
     @staticmethod
@@ -463,53 +571,39 @@ class AMPConvFunction(torch.autograd.Function):
         if dy is None:
             return (None,) * 11
         xq2, xkv2, w_in, w_out, qkv, kv, obar = ctx.saved_tensors
-        csr, shared = ctx.csr, ctx.shared
-        Nq, Nk, L, D, H = ctx.dims
-        dh = D // H
+        csr, (Nq, Nk), plan, sc = ctx.csr, ctx.dims, ctx.plan, ctx.scalars
+        L, D, dh, shared = plan.L, plan.D, plan.dh, plan.shared
         dev = dy.device
         need_xq, need_xkv = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        with torch.cuda.device(dev), gemm_precision(ctx.gemm):
+        with torch.cuda.device(dev), gemm_precision(plan.gemm):
             dy2 = dy.contiguous().view(Nq * L, D)
-            native = proj_native(ctx.gemm, dy2.dtype, D)
+            if plan.scaled:     # (one pass + one read-back per step: gradients are new every step)
+                st, narrow = operand_stats(dy2)
+                plan = plan.backward(narrow)
+                sc = sc.for_backward(st[0:1]) if plan.scaled else Scalars()
+            if plan.qkv_to_f32:                 # the saved projections as fp32 for the exact edge passes
+                qkv = planes_to_f32(qkv, ctx.scalars.qkv_bound, dh)
             # out-projection: rows with no in-edge contribute nothing (their obar is 0, and
             # the bias gradient masks them explicitly)
-            lists, am, bounds = ctx.lists, ctx.amax, ctx.bounds
-            # maxima of the gradients that are operands: [dY, dQ (shared: dQKV), dK | dV].  The scaled products serve dY
-            # only if it lies within 2^RANGE_LOG2 of its maximum too (one pass + one read-back per step: gradients are
-            # new every step); otherwise the whole backward pass takes the exact kernels
-            ag = None
-            if am is not None:
-                stg, narrow = operand_stats(dy2)
-                if narrow:
-                    ag = [stg[0:1], torch.zeros(1, dtype=torch.float32, device=dev), None]
-                else:
-                    am = None
-            planes = ctx.plane_format and ag is not None
-            scaledv = bounds is not None and not ctx.plane_format and ag is not None
-            if ctx.plane_format and not planes:           # the saved projections as fp32 for the exact edge passes
-                qkv = planes_to_f32(qkv, bounds[0:1], dh)
-            sl = (lambda t, i: t[i]) if am is not None else (lambda t, i: None)
-            pair = (lambda a, b: (a, b)) if am is not None else (lambda a, b: None)
-            if native:
+            if plan.native:
                 dw_out = torch.empty_like(w_out)
                 db_out = torch.empty(D, dtype=dy2.dtype, device=dev)
-                if lists:   # the listed nodes ARE the ones that pass the mask; dObar is read for destinations only
-                    proj_wgrad(dy2, obar, dw_out, db_out, L=L, nodes=lists['in'])
-                    dobar = proj_rows(dy2, ctx.images_t[-1], L=L, nodes=lists['in'])
-                elif planes:    # dObar / in-degree as two fp16 planes (the edge passes then carry no per-edge weight)
-                    proj_wgrad(dy2, obar, dw_out, db_out, csr.rowptr, L, amax=pair(sl(ag, 0), sl(am, 1)))
-                    proj_out_bound(w_out, True, None, ag[0], bounds[1:2])
-                    bounds[3:4].zero_()
-                    dobar = proj_rows_planes(dy2, ctx.images_t[-1], bounds[1:2], rowptr=csr.rowptr, L=L, row_scale=1,
-                                             amax=ag[0], out_amax=bounds[3:4], dh=dh)
-                elif scaledv:   # fp32 dObar, its maximum recorded by the product that writes it (bounds[1]; [3]: a copy)
-                    proj_wgrad(dy2, obar, dw_out, db_out, csr.rowptr, L, amax=pair(sl(ag, 0), sl(am, 1)))
-                    bounds[1:2].zero_()
-                    dobar = proj_rows(dy2, ctx.images_t[-1], amax=ag[0], out_amax=bounds[1:2])
-                    bounds[3:4].copy_(bounds[1:2])
+                if plan.lists:   # the listed nodes ARE the ones that pass the mask; dObar is read for destinations only
+                    proj_wgrad(dy2, obar, dw_out, db_out, L=L, nodes=plan.lists['in'])
+                    dobar = proj_rows(dy2, ctx.images_t[-1], L=L, nodes=plan.lists['in'])
                 else:
-                    proj_wgrad(dy2, obar, dw_out, db_out, csr.rowptr, L, amax=pair(sl(ag, 0), sl(am, 1)))
-                    dobar = proj_rows(dy2, ctx.images_t[-1], amax=sl(ag, 0))
+                    proj_wgrad(dy2, obar, dw_out, db_out, csr.rowptr, L, amax=(sc.dy, sc.obar))
+                    if plan.edge == 'planes':   # dObar / in-degree as two fp16 planes (the edge passes then carry no
+                        proj_out_bound(w_out, True, None, sc.dy, sc.dobar_bound)        # per-edge weight)
+                        sc.dobar_max.zero_()
+                        dobar = proj_rows_planes(dy2, ctx.images_t[-1], sc.dobar_bound, rowptr=csr.rowptr, L=L,
+                                                 row_scale=1, amax=sc.dy, out_amax=sc.dobar_max, dh=dh)
+                    elif plan.edge == 'views':  # fp32 dObar, its maximum recorded by the product that writes it
+                        sc.dobar_bound.zero_()
+                        dobar = proj_rows(dy2, ctx.images_t[-1], amax=sc.dy, out_amax=sc.dobar_bound)
+                        sc.dobar_max.copy_(sc.dobar_bound)       # (Scalars.for_forward)
+                    else:
+                        dobar = proj_rows(dy2, ctx.images_t[-1], amax=sc.dy)
             else:
                 scratch = torch.empty((1 + _lib.COLSUM_BLOCKS) * D, dtype=torch.float32, device=dev)
                 io = _lib.AMPCONV_BF16 if dy2.dtype == torch.bfloat16 else _lib.AMPCONV_F32
@@ -520,93 +614,49 @@ class AMPConvFunction(torch.autograd.Function):
                 dw_out = _tn_matmul(dy2, obar)
                 dobar = dy2.mm(w_out)                                      # [Nq*L, D]
             dOv = _view(dobar, 0, L, dh)
-            if shared:
-                dqkv = torch.empty(Nq * L, 3 * D, dtype=dy2.dtype, device=dev)
-                Qv, Kv, Vv = (_view(qkv, i * D, L, dh) for i in range(3))
-                dQv, dKv, dVv = (_view(dqkv, i * D, L, dh) for i in range(3))
-                dkv = None
-            else:
-                dqkv = torch.empty(Nq * L, D, dtype=dy2.dtype, device=dev)
-                dkv = torch.empty(Nk * L, 2 * D, dtype=dy2.dtype, device=dev)
-                Qv, Kv, Vv = _view(qkv, 0, L, dh), _view(kv, 0, L, dh), _view(kv, D, L, dh)
-                dQv, dKv, dVv = _view(dqkv, 0, L, dh), _view(dkv, 0, L, dh), _view(dkv, D, L, dh)
-            # softmax statistics (normaliser, delta) per edge: a by-product of the destination
-            # pass that saves the source pass its cross-lane reductions (include/ampconv.h)
-            stats = spos = None
-            nstat = lib.ampconv_softmax_stats_bytes(csr.num_edges, L, D, H, ctx.dtype) if SOFTMAX_STATS else 0
-            if nstat:
-                stats = torch.empty(nstat // 4, dtype=torch.float32, device=dev)
-                spos = csr.csc_positions()
-            plan, nch, ws = csr.hub_args('dst', L, D, 1)
-            if planes:
-                # both passes on the 16-bit matrix pipe; each records the maximum of what it writes (ag[1]: all of dQKV)
-                _lib.check(lib.ampconv_bwd_edge_dst_planes(Qv, Kv, Vv, dOv, csr.rowptr.data_ptr(), csr.col.data_ptr(),
-                                                           Nq, L, D, H, dQv, plan, nch, _ptr(ws), bounds.data_ptr(),
-                                                           _ptr(spos), _ptr(stats), ag[1].data_ptr(), _stream()),
-                           'ampconv_bwd_edge_dst_planes')
-                plan, nch, ws = csr.hub_args('src', L, D, 2)
-                _lib.check(lib.ampconv_bwd_edge_src_planes(Qv, Kv, Vv, dOv, csr.cscptr.data_ptr(), csr.crow.data_ptr(),
-                                                           Nk, L, D, H, dKv, dVv, plan, nch, _ptr(ws), bounds.data_ptr(),
-                                                           _ptr(stats), ag[1].data_ptr(), _stream()),
-                           'ampconv_bwd_edge_src_planes')
-            elif scaledv:
-                _lib.check(lib.ampconv_bwd_edge_dst_scaled(Qv, Kv, Vv, dOv, csr.rowptr.data_ptr(), csr.col.data_ptr(),
-                                                           Nq, L, D, H, dQv, plan, nch, _ptr(ws), bounds.data_ptr(),
-                                                           _ptr(spos), _ptr(stats), ag[1].data_ptr(), _stream()),
-                           'ampconv_bwd_edge_dst_scaled')
-                plan, nch, ws = csr.hub_args('src', L, D, 2)
-                _lib.check(lib.ampconv_bwd_edge_src_scaled(Qv, Kv, Vv, dOv, csr.cscptr.data_ptr(), csr.crow.data_ptr(),
-                                                           csr.cinv.data_ptr(), Nk, L, D, H, dKv, dVv, plan, nch, _ptr(ws),
-                                                           bounds.data_ptr(), _ptr(stats), ag[1].data_ptr(), _stream()),
-                           'ampconv_bwd_edge_src_scaled')
-            else:
-                # (scaled projections: the operand maximum of the two products that consume dQKV.  The destination pass
-                # records the maximum of dQ as it stores; dK | dV: one pass below -- the fp32 source-pass kernels have no
-                # register to spare for it (csrc/edge_mfma.hip); shared: one maximum, else dQ and dK | dV apart)
-                rc = lib.ampconv_bwd_edge_dst(Qv, Kv, Vv, dOv, csr.rowptr.data_ptr(), csr.col.data_ptr(),
-                                              Nq, L, D, H, dQv, plan, nch, _ptr(ws), _ptr(spos), _ptr(stats),
-                                              _ptr(sl(ag, 1)), ctx.dtype, _stream())
-                _lib.check(rc, 'ampconv_bwd_edge_dst')
-                plan, nch, ws = csr.hub_args('src', L, D, 2)
-                rc = lib.ampconv_bwd_edge_src(Qv, Kv, Vv, dOv, csr.cscptr.data_ptr(), csr.crow.data_ptr(),
-                                              csr.cinv.data_ptr(), Nk, L, D, H, dKv, dVv, plan, nch, _ptr(ws),
-                                              _ptr(stats), None, ctx.dtype, _stream())
-                _lib.check(rc, 'ampconv_bwd_edge_src')
-                if am is not None:
-                    if shared:
-                        absmax(dqkv[:, D:], ag[1])                # merged into the maximum of dQ
-                    else:
-                        ag[2] = absmax(dkv)
+            dqkv = torch.empty(Nq * L, (3 if shared else 1) * D, dtype=dy2.dtype, device=dev)
+            dkv = None if shared else torch.empty(Nk * L, 2 * D, dtype=dy2.dtype, device=dev)
+            Qv, Kv, Vv = _qkv_views(qkv, kv, L, D, dh)
+            dQv, dKv, dVv = _qkv_views(dqkv, dkv, L, D, dh)
+            stats = edge_bwd_dst(plan, csr, Qv, Kv, Vv, dOv, Nq, dQv, sc)
+            edge_bwd_src(plan, csr, Qv, Kv, Vv, dOv, Nk, dKv, dVv, stats, sc)
+            if plan.scaled and plan.edge == 'plain':
+                # (the operand maximum of the two products that consume dQKV: max |dQ| came from the destination pass,
+                # dK | dV take one pass here; shared: one maximum, else dQ and dK | dV apart)
+                if shared:
+                    absmax(dqkv[:, D:], sc.dqkv)                # merged into the maximum of dQ
+                else:
+                    sc.dkv = absmax(dkv)
             # in_proj_bias gradient without a pass over all of dQKV: softmax rows sum to 1, so the
             # column sum of dV over every source token equals the column sum of dObar over the rows
             # that receive messages, and dObar = dY Wo is linear in dY, so that sum is (masked column sum of
             # dY) Wo = db_out Wo: a [D] x [D, D] product instead of a second 20 GB reduction pass.  The K bias
             # shifts every score of a row equally, i.e. has gradient exactly 0 (torch's autograd returns ~1e-9 noise)
             db_v = None
-            if shared and dy2.dtype == torch.float32 and not native:
+            if shared and dy2.dtype == torch.float32 and not plan.native:
                 db_v = scratch[:D] @ w_out
             del dobar, stats
-            if native:
+            if plan.native:
                 # weight and bias gradients in one pass each (the column sums ride on the rows the product reads
                 # anyway: all three thirds of in_proj_bias.grad are the true sums, as autograd's are)
                 dw_in = torch.empty_like(w_in)
                 db_in = torch.empty(3 * D, dtype=dy2.dtype, device=dev)
-                if lists:   # the dQKV rows of a node without any edge are zeros (both edge passes wrote them)
-                    proj_wgrad(dqkv, xq2, dw_in, db_in, L=L, nodes=lists['any'])
+                if plan.lists:   # the dQKV rows of a node without any edge are zeros (both edge passes wrote them)
+                    proj_wgrad(dqkv, xq2, dw_in, db_in, L=L, nodes=plan.lists['any'])
                     dxq = dxkv = None
                     if need_xq:
-                        dxq2 = proj_rows(dqkv, ctx.images_t[0], L=L, nodes=lists['any'])
-                        _zero_unlisted(dxq2, lists['any'], Nq, L)
+                        dxq2 = proj_rows(dqkv, ctx.images_t[0], L=L, nodes=plan.lists['any'])
+                        _zero_unlisted(dxq2, plan.lists['any'], Nq, L)
                         dxq = dxq2.view(Nq, L * D)
                 elif shared:
-                    proj_wgrad(dqkv, xq2, dw_in, db_in, amax=pair(sl(ag, 1), sl(am, 0)))
-                    dxq = proj_rows(dqkv, ctx.images_t[0], amax=sl(ag, 1)).view(Nq, L * D) if need_xq else None
+                    proj_wgrad(dqkv, xq2, dw_in, db_in, amax=(sc.dqkv, sc.x))
+                    dxq = proj_rows(dqkv, ctx.images_t[0], amax=sc.dqkv).view(Nq, L * D) if need_xq else None
                     dxkv = None
                 else:
-                    proj_wgrad(dqkv, xq2, dw_in[:D], db_in[:D], amax=pair(sl(ag, 1), sl(am, 0)))
-                    proj_wgrad(dkv, xkv2, dw_in[D:], db_in[D:], amax=pair(sl(ag, 2), sl(am, 2)))
-                    dxq = proj_rows(dqkv, ctx.images_t[0], amax=sl(ag, 1)).view(Nq, L * D) if need_xq else None
-                    dxkv = proj_rows(dkv, ctx.images_t[1], amax=sl(ag, 2)).view(Nk, L * D) if need_xkv else None
+                    proj_wgrad(dqkv, xq2, dw_in[:D], db_in[:D], amax=(sc.dqkv, sc.x))
+                    proj_wgrad(dkv, xkv2, dw_in[D:], db_in[D:], amax=(sc.dkv, sc.xkv))
+                    dxq = proj_rows(dqkv, ctx.images_t[0], amax=sc.dqkv).view(Nq, L * D) if need_xq else None
+                    dxkv = proj_rows(dkv, ctx.images_t[1], amax=sc.dkv).view(Nk, L * D) if need_xkv else None
             elif shared:
                 dw_in = _tn_matmul(dqkv, xq2)
                 if db_v is not None:

@@ -160,9 +160,9 @@ int ampconv_bwd_edge_src_mfma(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t
                               ampconv_view_t dK, ampconv_view_t dV, HubArgs hub, StatsArgs st,
                               hipStream_t stream);
 
-// ---- workgroup-per-unit MFMA path (edge_block.hip): L <= 64, even dh <= 64, views aligned to two elements; fp32 or
-// bf16 storage (`bf16`), fp32 arithmetic.  The source pass of this path exists only with the statistics of the
-// destination pass.
+// ---- workgroup-per-unit MFMA path (edge_block_x3.hip): L <= 64, even dh <= 64, views aligned to two elements; fp32
+// storage as three bf16 planes per value (six partial products), bf16 storage as it lies (one product), fp32 accumulate on
+// the 16-bit matrix pipe.  The source pass of this path exists only with the statistics of the destination pass.
 bool ampconv_block_supported(int L, int D, int H, const ampconv_view_t *views, int n, bool bf16);
 int ampconv_block_stats_floats(int L);      // floats per (edge, head): 2 * 16 * ceil(L / 16)
 int ampconv_fwd_edge_block(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, const int32_t *rowptr,
@@ -175,20 +175,6 @@ int ampconv_bwd_edge_src_block(ampconv_view_t Q, ampconv_view_t K, ampconv_view_
                                const int32_t *cscptr, const int32_t *crow, const float *cinv, int64_t n_src,
                                int L, int D, int H, ampconv_view_t dK, ampconv_view_t dV, HubArgs hub,
                                const float *stats, bool bf16, hipStream_t stream);
-
-// ---- the same path on the 16-bit matrix pipe (edge_block_x3.hip: fp32 rows as three bf16 planes per value, six partial
-// products; bf16 rows as they lie, one product); `vec` = vec_of() of the views (4 or 2 elements)
-bool ampconv_block_x3_supported(int L, int D, int H, bool bf16);
-int ampconv_fwd_edge_block_x3(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, const int32_t *rowptr,
-                              const int32_t *col, const int32_t *qidx, int64_t n_rows, int L, int D, int H,
-                              ampconv_view_t O, HubArgs hub, int vec, bool bf16, hipStream_t stream);
-int ampconv_bwd_edge_dst_block_x3(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, ampconv_view_t dO,
-                                  const int32_t *rowptr, const int32_t *col, int64_t n_rows, int L, int D, int H,
-                                  ampconv_view_t dQ, HubArgs hub, StatsArgs sa, int vec, bool bf16, hipStream_t stream);
-int ampconv_bwd_edge_src_block_x3(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, ampconv_view_t dO,
-                                  const int32_t *cscptr, const int32_t *crow, const float *cinv, int64_t n_src, int L,
-                                  int D, int H, ampconv_view_t dK, ampconv_view_t dV, HubArgs hub, const float *stats,
-                                  int vec, bool bf16, hipStream_t stream);
 
 // ---- short token sequences (edge_small.hip): L <= 4, one wave per row, VALU only, fp32; views aligned to the lane's
 // vector width.  No softmax statistics.

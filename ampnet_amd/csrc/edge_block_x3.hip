@@ -1,14 +1,15 @@
-// Workgroup-per-unit edge kernels for the shapes of edge_block.hip (L <= 64, even dh <= 64) with fp32 storage (the reference's
-// AMPGCN class defaults: L = 40, D = 100, H = 2 -> dh = 50, src/ampnet/module/amp_gcn.py:21-35), OFF the FP32 pipe:
-// every fp32 tile is split into THREE bf16 planes on its way into LDS
+// Workgroup-per-unit edge kernels for the shapes the one-wave-per-unit kernels do not take: L <= 64, even dh <= 64.  fp32
+// storage (the reference's AMPGCN class defaults: L = 40, D = 100, H = 2 -> dh = 50, src/ampnet/module/amp_gcn.py:21-35)
+// runs OFF the FP32 pipe: every fp32 tile is split into THREE bf16 planes on its way into LDS
 //      x = h + m + l,   h = bf16(x), m = bf16(x - h), l = bf16(x - h - m)        (24 significand bits, no scale needed:
 //                                                                                 bf16 has fp32's exponent range)
 // and every product is the fp32 sum of six v_mfma_f32_16x16x32_bf16 partial products
 //      a b ~ a_l b_h + a_h b_l + a_m b_m + a_m b_h + a_h b_m + a_h b_h           (dropped: a_m b_l + a_l b_m + a_l b_l
 //                                                                                 <= 2^-24 |a b|)
 // -- 96 matrix-pipe cycles per 16 x 16 x 32 block instead of the 256 of eight v_mfma_f32_16x16x4_f32, and on the 16-bit
-// matrix pipe, which runs beside the vector ALU instead of on it.  Softmax, delta and all sums stay fp32; HBM traffic,
-// statistics hand-off and the long-segment plan are those of edge_block.hip (same entry points, same bytes).
+// matrix pipe, which runs beside the vector ALU instead of on it.  Softmax, delta and all sums stay fp32.  The source pass
+// exists only with the softmax statistics the destination pass hands over (include/ampconv.h).  (The fp32-MFMA kernels
+// that served these shapes up to round 5, edge_block.hip, were removed once these replaced them: see git history.)
 //
 // One WORKGROUP owns one (row, head) unit; wave w of its NT = ceil(L / 16) owns the unit's own tokens 16 w .. 16 w + 15
 // (the COLUMNS of every score tile), all waves share the LDS images of the streamed pair of tiles.  Per plane an image
@@ -17,7 +18,7 @@
 // the ds_read_b128 of the channel-product fragments and the ds_read_b64_tr_b16 of the token-product fragments are both
 // bank-conflict free (tools/lds_bank_check.py).
 // Reference arithmetic replaced: torch functional.py:6578-6594 per edge, the mean of amp_conv.py:11, and their autograd
-// backward -- as edge_block.hip.
+// backward.
 #include "mfma_tile.h"
 
 namespace {
@@ -1253,7 +1254,7 @@ __global__ __launch_bounds__(64 * NT, AMPCONV_XH_SRC_WAVES) void bwd_src_xh(XArg
 // accumulators, softmax and delta stay fp32.  Nothing is pre-scaled (that would round the operands again): the scores meet
 // log2e / sqrt(dh) inside the exponential, 1 / in-degree is applied to dS and to the weights that multiply dObar, and
 // delta is handed over in the units of the raw dObar V^T product.  Views: strides in bf16 elements, bases and strides
-// even (4-byte pieces) at least.  These kernels replace the fp32-MFMA kernels of edge_block.hip for bf16 rows.
+// even (4-byte pieces) at least.
 template <int EV, int NT, int KS>
 struct StageB {                                             // EV = bf16 elements per lane and load (2 or 4)
   static constexpr int DVP = 32 * KS / EV;
@@ -1693,22 +1694,32 @@ XArgs x3_args(int64_t n_rows, int L, int D, int H) {
   return a;
 }
 
+// the widest vector (4 or 2 elements of esize bytes) that every view's base and strides allow
+int vec_of(const ampconv_view_t *views, int n, int dh, int esize) {
+  int vec = dh % 4 == 0 ? 4 : 2;
+  for (int i = 0; i < n; ++i) {
+    const ampconv_view_t &v = views[i];
+    while (vec > 1 && (((uintptr_t)v.ptr % (esize * vec)) || v.node_stride % vec || v.row_stride % vec ||
+                       v.head_stride % vec))
+      vec >>= 1;
+  }
+  return vec;
+}
 }  // namespace
 
-// developer A/B switch: AMPCONV_BLOCK_X3=0 keeps these shapes on the fp32-MFMA kernels of edge_block.hip
-bool ampconv_block_x3_supported(int L, int D, int H, bool bf16) {
-  static const bool on = [] {
-    const char *e = getenv("AMPCONV_BLOCK_X3");
-    return !(e && e[0] == '0');
-  }();
+bool ampconv_block_supported(int L, int D, int H, const ampconv_view_t *views, int n, bool bf16) {
   const int dh = D / H;
-  (void)bf16;       // fp32 rows: three bf16 planes split in the kernel; bf16 rows: one plane as it lies
-  return on && L >= 1 && L <= 64 && dh >= 2 && dh <= 64 && dh % 2 == 0;
+  if (!(L >= 1 && L <= 64 && dh >= 2 && dh <= 64 && dh % 2 == 0)) return false;
+  return vec_of(views, n, dh, bf16 ? 2 : 4) >= 2;
 }
 
-int ampconv_fwd_edge_block_x3(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, const int32_t *rowptr,
-                              const int32_t *col, const int32_t *qidx, int64_t n_rows, int L, int D, int H,
-                              ampconv_view_t O, HubArgs hub, int vec, bool bf16, hipStream_t stream) {
+int ampconv_block_stats_floats(int L) { return 2 * 16 * ((L + 15) / 16); }
+
+int ampconv_fwd_edge_block(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, const int32_t *rowptr,
+                           const int32_t *col, const int32_t *qidx, int64_t n_rows, int L, int D, int H,
+                           ampconv_view_t O, HubArgs hub, bool bf16, hipStream_t stream) {
+  const ampconv_view_t views[] = {Q, K, V, O};
+  const int vec = vec_of(views, 4, D / H, bf16 ? 2 : 4);
   XArgs a = x3_args(n_rows, L, D, H);
   a.hub = hub;
   a.Q = Q; a.K = K; a.V = V; a.O = O;
@@ -1718,9 +1729,11 @@ int ampconv_fwd_edge_block_x3(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t
   return launch_x3(a, ntok, x3_pick<XFwd>(vec, ntok, ks), stream);
 }
 
-int ampconv_bwd_edge_dst_block_x3(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, ampconv_view_t dO,
-                                  const int32_t *rowptr, const int32_t *col, int64_t n_rows, int L, int D, int H,
-                                  ampconv_view_t dQ, HubArgs hub, StatsArgs sa, int vec, bool bf16, hipStream_t stream) {
+int ampconv_bwd_edge_dst_block(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, ampconv_view_t dO,
+                               const int32_t *rowptr, const int32_t *col, int64_t n_rows, int L, int D, int H,
+                               ampconv_view_t dQ, HubArgs hub, StatsArgs sa, bool bf16, hipStream_t stream) {
+  const ampconv_view_t views[] = {Q, K, V, dO, dQ};
+  const int vec = vec_of(views, 5, D / H, bf16 ? 2 : 4);
   XArgs a = x3_args(n_rows, L, D, H);
   a.hub = hub;
   a.Q = Q; a.K = K; a.V = V; a.dO = dO; a.O = dQ;
@@ -1731,11 +1744,13 @@ int ampconv_bwd_edge_dst_block_x3(ampconv_view_t Q, ampconv_view_t K, ampconv_vi
   return launch_x3(a, ntok, sa.stats ? x3_pick<XDstS>(vec, ntok, ks) : x3_pick<XDst>(vec, ntok, ks), stream);
 }
 
-int ampconv_bwd_edge_src_block_x3(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, ampconv_view_t dO,
-                                  const int32_t *cscptr, const int32_t *crow, const float *cinv, int64_t n_src, int L,
-                                  int D, int H, ampconv_view_t dK, ampconv_view_t dV, HubArgs hub, const float *stats,
-                                  int vec, bool bf16, hipStream_t stream) {
+int ampconv_bwd_edge_src_block(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, ampconv_view_t dO,
+                               const int32_t *cscptr, const int32_t *crow, const float *cinv, int64_t n_src,
+                               int L, int D, int H, ampconv_view_t dK, ampconv_view_t dV, HubArgs hub,
+                               const float *stats, bool bf16, hipStream_t stream) {
   if (!stats) return AMPCONV_E_BADARG;
+  const ampconv_view_t views[] = {Q, K, V, dO, dK, dV};
+  const int vec = vec_of(views, 6, D / H, bf16 ? 2 : 4);
   XArgs a = x3_args(n_src, L, D, H);
   a.hub = hub;
   a.Q = Q; a.K = K; a.V = V; a.dO = dO; a.dK = dK; a.dV = dV;

@@ -179,21 +179,9 @@ class _PartitionedFunction(torch.autograd.Function):
             dkv_all = torch.empty(NP * L, 2 * D, dtype=torch.float32, device=dev)     # partial sums, all sources
             dQv = F_._view(dq, 0, L, dh)
             dKv, dVv = F_._view(dkv_all, 0, L, dh), F_._view(dkv_all, D, L, dh)
-            stats = spos = None
-            nstat = lib.ampconv_softmax_stats_bytes(csr.num_edges, L, D, H, ctx.dtype) if F_.SOFTMAX_STATS else 0
-            if nstat:
-                stats = torch.empty(nstat // 4, dtype=torch.float32, device=dev)
-                spos = csr.csc_positions()
-            plan, nch, ws = csr.hub_args('dst', L, D, 1)
-            rc = lib.ampconv_bwd_edge_dst(Qv, Kv, Vv, dOv, csr.rowptr.data_ptr(), csr.col.data_ptr(), nl, L, D, H,
-                                          dQv, plan, nch, F_._ptr(ws), F_._ptr(spos), F_._ptr(stats), None,
-                                          ctx.dtype, _stream())
-            _lib.check(rc, 'ampconv_bwd_edge_dst')
-            plan, nch, ws = csr.hub_args('src', L, D, 2)
-            rc = lib.ampconv_bwd_edge_src(Qv, Kv, Vv, dOv, csr.cscptr.data_ptr(), csr.crow.data_ptr(),
-                                          csr.cinv.data_ptr(), NP, L, D, H, dKv, dVv, plan, nch, F_._ptr(ws),
-                                          F_._ptr(stats), None, ctx.dtype, _stream())
-            _lib.check(rc, 'ampconv_bwd_edge_src')
+            plan = F_.LayerPlan(L, D, H, dtype=ctx.dtype)                   # the plain pair
+            stats = F_.edge_bwd_dst(plan, csr, Qv, Kv, Vv, dOv, nl, dQv, F_.Scalars())
+            F_.edge_bwd_src(plan, csr, Qv, Kv, Vv, dOv, NP, dKv, dVv, stats, F_.Scalars())
             del dobar, stats
             # this rank's rows of dK|dV, summed over ranks: in flight while the Q-side products run
             dkv, work = part.reduce_scatter_rows_start(dkv_all)

@@ -53,9 +53,9 @@ def test_block_path_vs_fp64_oracle(shape, scaled, dev, monkeypatch):
 
 
 def test_block_path_error_table_vs_fp64(dev, monkeypatch):
-    """max error / max entry against fp64 at the class-default shape: both 16-bit variants next to the fp32-MFMA kernels
-    they replace (AMPCONV_BLOCK_X3=0 is read once per process, so those run through the generic switch's sibling: the
-    numbers of the fp32 kernels are in DESIGN.md 4d); both must stay under the bar the fp32 path is held to (5e-6)."""
+    """max error / max entry against fp64 at the class-default shape: both 16-bit variants (the numbers of the fp32-MFMA
+    kernels they replaced, since removed, are in DESIGN.md 4d); both must stay under the bar the fp32 path is held to
+    (5e-6)."""
     from ampnet_amd.conv import functional as F_
     N, E, L, D, H = 800, 8000, 40, 100, 2
     layer, x, dy, ei = _make(N, E, L, D, H, dev, seed=31, x_scale=2.0, hub=False)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # SQ counters + HBM traffic of the workgroup-per-unit kernels on the AMPGCN class-default shape (developer tool).
-#   tools/prof_x3.sh <tag> [--scaled]    (environment: AMPCONV_BLOCK_X3, AMPCONV_LIB_PATH)
+#   tools/prof_x3.sh <tag> [--scaled]    (environment: AMPCONV_LIB_PATH)
 tag=${1:-x3}; shift
 ARGS="100000 1000000 40 100 2 $@"           # e.g. --scaled: the bound-carrying entry points (two fp16 planes)
 SQ_DIR=${SQ_DIR:-sq_r5} bash tools/prof_sq.sh $tag $ARGS || exit 1
