@@ -195,6 +195,35 @@ int ampconv_hub_combine(const void *plan, int64_t n_chunks, const float *P, ampc
                         const int32_t *ptr_for_mean, int L, int D, int H, float scale, int out_bf16,
                         hipStream_t stream, float *absmax = nullptr);
 
+// partial-tile view of the hub workspace: tile t (0: O / dQ / dK, 1: dV), chunk c, token l, channel cc at
+// P[((t * n_chunks + c) * L + l) * D + cc]
+static inline ampconv_view_t hub_partial_view(void *ws, int tile, int64_t n_chunks, int L, int D, int H) {
+  return ampconv_view_t{(float *)ws + tile * n_chunks * L * D, (int64_t)L * D, (int64_t)D, (int64_t)(D / H)};
+}
+
+// One edge pass into the N outputs `outs` (O or dQ: N = 1; dK, dV: N = 2).  launch(n, hub, views, absmax) runs the
+// family's kernel over n rows with those HubArgs into those N output views.  Without a plan: one plain pass over the
+// n_rows rows.  With one (long segments): the main pass over the rows (mode 1, rows longer than a chunk skipped), the
+// hub pass over the chunks into partial tiles of hub_ws (mode 2), then the ordered combine of each output's tiles:
+// the mean over the row where ptr_for_mean is given (forward), else times scale[i]; bf16 outputs if out_bf16.
+// absmax (out_absmax, for the families whose kernels record it, else nullptr): recorded by the main pass and the
+// combine -- not by the hub pass, whose partial tiles are not what the pass writes.
+template <int N, typename Launch>
+int run_edge_pass(const Launch &launch, int64_t n_rows, const ampconv_view_t (&outs)[N], const void *hub_plan,
+                  int64_t hub_chunks, void *hub_ws, int L, int D, int H, const int32_t *ptr_for_mean,
+                  const float (&scale)[N], int out_bf16, float *absmax, hipStream_t stream) {
+  if (!(hub_plan && hub_chunks > 0 && hub_ws)) return launch(n_rows, HubArgs{nullptr, 0}, outs, absmax);
+  if (int rc = launch(n_rows, HubArgs{(const int32_t *)hub_plan, 1}, outs, absmax)) return rc;
+  ampconv_view_t P[N];
+  for (int i = 0; i < N; ++i) P[i] = hub_partial_view(hub_ws, i, hub_chunks, L, D, H);
+  if (int rc = launch(hub_chunks, HubArgs{(const int32_t *)hub_plan, 2}, P, nullptr)) return rc;
+  for (int i = 0; i < N; ++i)
+    if (int rc = ampconv_hub_combine(hub_plan, hub_chunks, (const float *)P[i].ptr, outs[i], ptr_for_mean, L, D, H,
+                                     scale[i], out_bf16, stream, absmax))
+      return rc;
+  return AMPCONV_OK;
+}
+
 // ---- bf16-storage path (edge_mfma_bf16.hip): L <= 20, dh == 32, 16-byte aligned bf16 views
 bool ampconv_bf16_supported(int L, int D, int H, const ampconv_view_t *views, int n);
 int ampconv_fwd_edge_bf16(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, const int32_t *rowptr,

@@ -1767,20 +1767,6 @@ int ampconv_bwd_edge_src_block(ampconv_view_t Q, ampconv_view_t K, ampconv_view_
 // ---------------------------------------------------------------------------------------------------------------------
 // C-ABI of the scaled kernels (include/ampconv.h, "edge phase on fp32 views with operand bounds")
 namespace {
-// views of two-float vectors at least: rows, heads and nodes an even number of elements apart, 8-byte aligned base
-int x3_vec(const ampconv_view_t *views, int n, int dh) {
-  int vec = dh % 4 == 0 ? 4 : 2;
-  for (int i = 0; i < n; ++i) {
-    const ampconv_view_t &v = views[i];
-    if (!v.ptr) return 0;
-    while (vec > 1 && (((uintptr_t)v.ptr % (4 * vec)) || v.node_stride % vec || v.row_stride % vec || v.head_stride % vec))
-      vec >>= 1;
-  }
-  return vec;
-}
-ampconv_view_t x3_partial_view(void *ws, int64_t tile, int64_t n_chunks, int L, int D, int H) {
-  return ampconv_view_t{(float *)ws + tile * n_chunks * L * D, (int64_t)L * D, (int64_t)D, (int64_t)(D / H)};
-}
 int x3_check(int64_t n, int L, int D, int H, const float *bounds) {
   if (L <= 0 || D <= 0 || H <= 0 || D % H != 0 || n < 0 || !bounds) return AMPCONV_E_BADARG;
   if (!ampconv_scaled_supported(L, D, H)) return AMPCONV_E_DTYPE;
@@ -1801,26 +1787,21 @@ extern "C" int ampconv_fwd_edge_scaled(ampconv_view_t Q, ampconv_view_t K, ampco
                                        void *stream) {
   if (int rc = x3_check(n_rows, L, D, H, bounds)) return rc;
   if (n_rows == 0) return AMPCONV_OK;
+  // (views of two-float vectors at least: rows, heads and nodes an even number of elements apart, 8-byte aligned base)
   const ampconv_view_t views[] = {Q, K, V, O};
-  const int vec = x3_vec(views, 4, D / H), ntok = (L + 15) / 16, ks = D / H > 32 ? 2 : 1;
-  if (vec < 2 || !rowptr) return AMPCONV_E_BADARG;
+  if (!view_ok(Q) || !view_ok(K) || !view_ok(V) || !view_ok(O) || vec_of(views, 4, D / H, 4) < 2 || !rowptr)
+    return AMPCONV_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
+  const int ntok = (L + 15) / 16, ks = D / H > 32 ? 2 : 1;
   XArgs a = x3_args(n_rows, L, D, H);
-  a.Q = Q; a.K = K; a.V = V; a.O = O;
+  a.Q = Q; a.K = K; a.V = V;
   a.ptr = rowptr; a.idx = col; a.bounds = bounds;
-  if (hub_plan && hub_chunks > 0 && hub_ws) {          // long segments: main + hub + combine
-    a.hub = HubArgs{(const int32_t *)hub_plan, 1};
-    if (int rc = launch_x3(a, ntok, x3_pick<HFwd>(vec, ntok, ks), st, 0, 2)) return rc;
-    const ampconv_view_t P = x3_partial_view(hub_ws, 0, hub_chunks, L, D, H);
-    a.O = P;
-    a.hub.mode = 2;
-    a.n_units = hub_chunks * H;
-    const ampconv_view_t pviews[] = {Q, K, V, P};
-    const int pvec = x3_vec(pviews, 4, D / H);
-    if (int rc = launch_x3(a, ntok, x3_pick<HFwd>(pvec, ntok, ks), st, 0, 2)) return rc;
-    return ampconv_hub_combine(hub_plan, hub_chunks, (const float *)P.ptr, O, rowptr, L, D, H, 1.f, 0, st);
-  }
-  return launch_x3(a, ntok, x3_pick<HFwd>(vec, ntok, ks), st, 0, 2);
+  auto run = [&](int64_t n, HubArgs hub, const ampconv_view_t *o, float *) {
+    const ampconv_view_t v[] = {Q, K, V, o[0]};
+    a.hub = hub; a.n_units = n * H; a.O = o[0];
+    return launch_x3(a, ntok, x3_pick<HFwd>(vec_of(v, 4, D / H, 4), ntok, ks), st, 0, 2);
+  };
+  return run_edge_pass(run, n_rows, {O}, hub_plan, hub_chunks, hub_ws, L, D, H, rowptr, {1.f}, 0, nullptr, st);
 }
 
 extern "C" int ampconv_bwd_edge_dst_scaled(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, ampconv_view_t dObar,
@@ -1832,28 +1813,24 @@ extern "C" int ampconv_bwd_edge_dst_scaled(ampconv_view_t Q, ampconv_view_t K, a
   if (stats && (!spos || (uintptr_t)stats % 16 != 0)) return AMPCONV_E_BADARG;
   if (n_rows == 0) return AMPCONV_OK;
   const ampconv_view_t views[] = {Q, K, V, dObar, dQ};
-  const int vec = x3_vec(views, 5, D / H), ntok = (L + 15) / 16, ks = D / H > 32 ? 2 : 1;
-  if (vec < 2 || !rowptr) return AMPCONV_E_BADARG;
+  if (!view_ok(Q) || !view_ok(K) || !view_ok(V) || !view_ok(dObar) || !view_ok(dQ) || vec_of(views, 5, D / H, 4) < 2 ||
+      !rowptr)
+    return AMPCONV_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
+  const int ntok = (L + 15) / 16, ks = D / H > 32 ? 2 : 1;
   XArgs a = x3_args(n_rows, L, D, H);
-  a.Q = Q; a.K = K; a.V = V; a.dO = dObar; a.O = dQ;
-  a.ptr = rowptr; a.idx = col; a.bounds = bounds; a.absmax = out_absmax;
+  a.Q = Q; a.K = K; a.V = V; a.dO = dObar;
+  a.ptr = rowptr; a.idx = col; a.bounds = bounds;
   a.spos = spos; a.stats = stats;
   a.oscale = 1.f / sqrtf((float)a.dh);
-  auto pick = [&](int v) { return stats ? x3_pick<HDstS>(v, ntok, ks) : x3_pick<HDst>(v, ntok, ks); };
-  if (hub_plan && hub_chunks > 0 && hub_ws) {
-    a.hub = HubArgs{(const int32_t *)hub_plan, 1};
-    if (int rc = launch_x3(a, ntok, pick(vec), st, 0, 2)) return rc;
-    const ampconv_view_t P = x3_partial_view(hub_ws, 0, hub_chunks, L, D, H);
-    a.O = P;
-    a.absmax = nullptr;                                // partial tiles: the combine pass records what it writes
-    a.hub.mode = 2;
-    a.n_units = hub_chunks * H;
-    const ampconv_view_t pviews[] = {Q, K, V, dObar, P};
-    if (int rc = launch_x3(a, ntok, pick(x3_vec(pviews, 5, D / H)), st, 0, 2)) return rc;
-    return ampconv_hub_combine(hub_plan, hub_chunks, (const float *)P.ptr, dQ, nullptr, L, D, H, a.oscale, 0, st, out_absmax);
-  }
-  return launch_x3(a, ntok, pick(vec), st, 0, 2);
+  auto run = [&](int64_t n, HubArgs hub, const ampconv_view_t *o, float *absmax) {
+    const ampconv_view_t v[] = {Q, K, V, dObar, o[0]};
+    const int vec = vec_of(v, 5, D / H, 4);
+    a.hub = hub; a.n_units = n * H; a.O = o[0]; a.absmax = absmax;
+    return launch_x3(a, ntok, stats ? x3_pick<HDstS>(vec, ntok, ks) : x3_pick<HDst>(vec, ntok, ks), st, 0, 2);
+  };
+  return run_edge_pass(run, n_rows, {dQ}, hub_plan, hub_chunks, hub_ws, L, D, H, nullptr, {a.oscale}, 0, out_absmax,
+                       st);
 }
 
 extern "C" int ampconv_bwd_edge_src_scaled(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, ampconv_view_t dObar,
@@ -1865,29 +1842,21 @@ extern "C" int ampconv_bwd_edge_src_scaled(ampconv_view_t Q, ampconv_view_t K, a
   if (!stats || (uintptr_t)stats % 16 != 0 || !cinv) return AMPCONV_E_BADARG;      // this pass exists only with the hand-off
   if (n_src == 0) return AMPCONV_OK;
   const ampconv_view_t views[] = {Q, K, V, dObar, dK, dV};
-  const int vec = x3_vec(views, 6, D / H), ntok = (L + 15) / 16, ks = D / H > 32 ? 2 : 1;
-  if (vec < 2 || !cscptr) return AMPCONV_E_BADARG;
+  if (!view_ok(Q) || !view_ok(K) || !view_ok(V) || !view_ok(dObar) || !view_ok(dK) || !view_ok(dV) ||
+      vec_of(views, 6, D / H, 4) < 2 || !cscptr)
+    return AMPCONV_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
+  const int ntok = (L + 15) / 16, ks = D / H > 32 ? 2 : 1;
   XArgs a = x3_args(n_src, L, D, H);
-  a.Q = Q; a.K = K; a.V = V; a.dO = dObar; a.dK = dK; a.dV = dV;
-  a.ptr = cscptr; a.idx = crow; a.cinv = cinv; a.bounds = bounds; a.absmax = out_absmax;
+  a.Q = Q; a.K = K; a.V = V; a.dO = dObar;
+  a.ptr = cscptr; a.idx = crow; a.cinv = cinv; a.bounds = bounds;
   a.stats = const_cast<float *>(stats);
   a.oscale = 1.f / sqrtf((float)a.dh);
-  const int extra = 2 * 16 * ntok * (int)sizeof(float);
-  if (hub_plan && hub_chunks > 0 && hub_ws) {
-    a.hub = HubArgs{(const int32_t *)hub_plan, 1};
-    if (int rc = launch_x3(a, ntok, x3_pick<HSrc>(vec, ntok, ks), st, extra, 2)) return rc;
-    const ampconv_view_t PK = x3_partial_view(hub_ws, 0, hub_chunks, L, D, H), PV = x3_partial_view(hub_ws, 1, hub_chunks, L, D, H);
-    a.dK = PK;
-    a.dV = PV;
-    a.absmax = nullptr;
-    a.hub.mode = 2;
-    a.n_units = hub_chunks * H;
-    const ampconv_view_t pviews[] = {Q, K, V, dObar, PK, PV};
-    if (int rc = launch_x3(a, ntok, x3_pick<HSrc>(x3_vec(pviews, 6, D / H), ntok, ks), st, extra, 2)) return rc;
-    if (int rc = ampconv_hub_combine(hub_plan, hub_chunks, (const float *)PK.ptr, dK, nullptr, L, D, H, a.oscale, 0, st, out_absmax))
-      return rc;
-    return ampconv_hub_combine(hub_plan, hub_chunks, (const float *)PV.ptr, dV, nullptr, L, D, H, 1.f, 0, st, out_absmax);
-  }
-  return launch_x3(a, ntok, x3_pick<HSrc>(vec, ntok, ks), st, extra, 2);
+  auto run = [&](int64_t n, HubArgs hub, const ampconv_view_t *o, float *absmax) {
+    const ampconv_view_t v[] = {Q, K, V, dObar, o[0], o[1]};
+    a.hub = hub; a.n_units = n * H; a.dK = o[0]; a.dV = o[1]; a.absmax = absmax;
+    return launch_x3(a, ntok, x3_pick<HSrc>(vec_of(v, 6, D / H, 4), ntok, ks), st, 2 * 16 * ntok * (int)sizeof(float), 2);
+  };
+  return run_edge_pass(run, n_src, {dK, dV}, hub_plan, hub_chunks, hub_ws, L, D, H, nullptr, {a.oscale, 1.f}, 0,
+                       out_absmax, st);
 }

@@ -703,10 +703,6 @@ inline bool plane_view_ok(const ampconv_view_t &v, int dh) {
 inline bool f32_view_ok(const ampconv_view_t &v) {
   return v.ptr && ((uintptr_t)v.ptr % 16 == 0) && (v.head_stride % 4 == 0) && (v.node_stride % 4 == 0) && (v.row_stride % 4 == 0);
 }
-// partial-tile view of the hub workspace (edge_api.hip): chunk c, token l, channel cc at P[(c * L + l) * D + cc]
-ampconv_view_t partial_view(void *ws, int64_t tile, int64_t n_chunks, int L, int D, int H) {
-  return ampconv_view_t{(float *)ws + tile * n_chunks * L * D, (int64_t)L * D, (int64_t)D, (int64_t)(D / H)};
-}
 int check_shape(int64_t n, int L, int D, int H, const float *bounds) {
   if (L <= 0 || D <= 0 || H <= 0 || D % H != 0 || n < 0 || !bounds) return AMPCONV_E_BADARG;
   if (L > kLmax || (D / H != DH && D / H != DH / 2)) return AMPCONV_E_DTYPE;
@@ -728,22 +724,13 @@ extern "C" int ampconv_fwd_edge_planes(ampconv_view_t Q, ampconv_view_t K, ampco
   if (!plane_view_ok(Q, D / H) || !plane_view_ok(K, D / H) || !plane_view_ok(V, D / H) || !f32_view_ok(O) || !rowptr) return AMPCONV_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
   Args a{};
-  a.Q = Q; a.K = K; a.V = V; a.O = O;
+  a.Q = Q; a.K = K; a.V = V;
   a.ptr = rowptr; a.idx = col; a.bounds = bounds; a.L = L; a.H = H;
-  if (hub_plan && hub_chunks > 0 && hub_ws) {          // long segments: main + hub + combine
-    a.hub = HubArgs{(const int32_t *)hub_plan, 1};
-    a.n_units = n_rows * H;
-    if (int rc = launch_fwd(a, L, D / H == DH / 2, st)) return rc;
-    const ampconv_view_t P = partial_view(hub_ws, 0, hub_chunks, L, D, H);
-    a.O = P;
-    a.hub.mode = 2;
-    a.n_units = hub_chunks * H;
-    if (int rc = launch_fwd(a, L, D / H == DH / 2, st)) return rc;
-    return ampconv_hub_combine(hub_plan, hub_chunks, (const float *)P.ptr, O, rowptr, L, D, H, 1.f, 0, st);
-  }
-  a.hub = HubArgs{nullptr, 0};
-  a.n_units = n_rows * H;
-  return launch_fwd(a, L, D / H == DH / 2, st);
+  auto run = [&](int64_t n, HubArgs hub, const ampconv_view_t *o, float *) {
+    a.hub = hub; a.n_units = n * H; a.O = o[0];
+    return launch_fwd(a, L, D / H == DH / 2, st);
+  };
+  return run_edge_pass(run, n_rows, {O}, hub_plan, hub_chunks, hub_ws, L, D, H, rowptr, {1.f}, 0, nullptr, st);
 }
 
 extern "C" int ampconv_bwd_edge_dst_planes(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, ampconv_view_t dObar,
@@ -758,25 +745,15 @@ extern "C" int ampconv_bwd_edge_dst_planes(ampconv_view_t Q, ampconv_view_t K, a
     return AMPCONV_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
   Args a{};
-  a.Q = Q; a.K = K; a.V = V; a.dO = dObar; a.O = dQ;
-  a.ptr = rowptr; a.idx = col; a.bounds = bounds; a.absmax = out_absmax; a.L = L; a.H = H;
+  a.Q = Q; a.K = K; a.V = V; a.dO = dObar;
+  a.ptr = rowptr; a.idx = col; a.bounds = bounds; a.L = L; a.H = H;
   a.spos = spos; a.stats = stats;
-  if (hub_plan && hub_chunks > 0 && hub_ws) {
-    a.hub = HubArgs{(const int32_t *)hub_plan, 1};
-    a.n_units = n_rows * H;
-    if (int rc = launch_dst(a, L, D / H == DH / 2, st)) return rc;
-    const ampconv_view_t P = partial_view(hub_ws, 0, hub_chunks, L, D, H);
-    a.O = P;
-    a.absmax = nullptr;                                // partial tiles: the combine pass records what it writes
-    a.hub.mode = 2;
-    a.n_units = hub_chunks * H;
-    if (int rc = launch_dst(a, L, D / H == DH / 2, st)) return rc;
-    return ampconv_hub_combine(hub_plan, hub_chunks, (const float *)P.ptr, dQ, nullptr, L, D, H, 1.f / sqrtf((float)(D / H)),
-                               0, st, out_absmax);
-  }
-  a.hub = HubArgs{nullptr, 0};
-  a.n_units = n_rows * H;
-  return launch_dst(a, L, D / H == DH / 2, st);
+  auto run = [&](int64_t n, HubArgs hub, const ampconv_view_t *o, float *absmax) {
+    a.hub = hub; a.n_units = n * H; a.O = o[0]; a.absmax = absmax;
+    return launch_dst(a, L, D / H == DH / 2, st);
+  };
+  return run_edge_pass(run, n_rows, {dQ}, hub_plan, hub_chunks, hub_ws, L, D, H, nullptr,
+                       {1.f / sqrtf((float)(D / H))}, 0, out_absmax, st);
 }
 
 extern "C" int ampconv_bwd_edge_src_planes(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, ampconv_view_t dObar,
@@ -792,26 +769,13 @@ extern "C" int ampconv_bwd_edge_src_planes(ampconv_view_t Q, ampconv_view_t K, a
     return AMPCONV_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
   Args a{};
-  a.Q = Q; a.K = K; a.V = V; a.dO = dObar; a.dK = dK; a.dV = dV;
-  a.ptr = cscptr; a.idx = crow; a.bounds = bounds; a.absmax = out_absmax; a.L = L; a.H = H;
+  a.Q = Q; a.K = K; a.V = V; a.dO = dObar;
+  a.ptr = cscptr; a.idx = crow; a.bounds = bounds; a.L = L; a.H = H;
   a.stats = const_cast<float *>(stats);
-  if (hub_plan && hub_chunks > 0 && hub_ws) {
-    a.hub = HubArgs{(const int32_t *)hub_plan, 1};
-    a.n_units = n_src * H;
-    if (int rc = launch_src(a, L, D / H == DH / 2, st)) return rc;
-    const ampconv_view_t PK = partial_view(hub_ws, 0, hub_chunks, L, D, H), PV = partial_view(hub_ws, 1, hub_chunks, L, D, H);
-    a.dK = PK;
-    a.dV = PV;
-    a.absmax = nullptr;
-    a.hub.mode = 2;
-    a.n_units = hub_chunks * H;
-    if (int rc = launch_src(a, L, D / H == DH / 2, st)) return rc;
-    if (int rc = ampconv_hub_combine(hub_plan, hub_chunks, (const float *)PK.ptr, dK, nullptr, L, D, H,
-                                     1.f / sqrtf((float)(D / H)), 0, st, out_absmax))
-      return rc;
-    return ampconv_hub_combine(hub_plan, hub_chunks, (const float *)PV.ptr, dV, nullptr, L, D, H, 1.f, 0, st, out_absmax);
-  }
-  a.hub = HubArgs{nullptr, 0};
-  a.n_units = n_src * H;
-  return launch_src(a, L, D / H == DH / 2, st);
+  auto run = [&](int64_t n, HubArgs hub, const ampconv_view_t *o, float *absmax) {
+    a.hub = hub; a.n_units = n * H; a.dK = o[0]; a.dV = o[1]; a.absmax = absmax;
+    return launch_src(a, L, D / H == DH / 2, st);
+  };
+  return run_edge_pass(run, n_src, {dK, dV}, hub_plan, hub_chunks, hub_ws, L, D, H, nullptr,
+                       {1.f / sqrtf((float)(D / H)), 1.f}, 0, out_absmax, st);
 }

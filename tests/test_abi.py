@@ -110,6 +110,63 @@ def test_abi_version_mismatch_fails_loudly(built, monkeypatch):
         _lib.load()
 
 
+def test_softmax_stats_bytes_follows_the_family_of_the_destination_pass(built, monkeypatch):
+    """ampconv_softmax_stats_bytes sizes the buffer the destination pass writes its statistics into: it must name the
+    layout of the very family that pass picks, for both dtypes and under both environment switches.  Layouts: 40 floats
+    per (edge, head) for edge_mfma.hip, 2 * 16 * ceil(L / 16) for the workgroup-per-unit kernels, none for the others.
+    Host code only: no kernel runs."""
+    from ampnet_amd import _lib
+    lib = _lib.load()
+
+    def small(L, D, H):                                          # edge_small.hip: L <= 4, a head = 4 .. 32 lanes of a wave
+        dh = D // H
+        return L <= 4 and any(D % v == 0 and dh % v == 0 and D // v <= 64 and dh // v in (4, 8, 16, 32) for v in (1, 2, 4))
+
+    def expected(E, L, D, H, bf16, force_generic, small_off):
+        dh = D // H
+        one_wave = L <= 20 and dh in (16, 32)                    # edge_mfma.hip / edge_mfma_bf16.hip
+        block = L <= 64 and 2 <= dh <= 64 and dh % 2 == 0        # edge_block_x3.hip
+        if bf16:
+            per_unit = 0 if one_wave or not block else 32 * ((L + 15) // 16)
+        elif force_generic or (not small_off and small(L, D, H)):
+            per_unit = 0
+        elif one_wave:
+            per_unit = 40
+        else:
+            per_unit = 32 * ((L + 15) // 16) if block else 0
+        return E * H * per_unit * 4
+
+    def switch(name, value):                                     # read by the library on every call
+        if value is None:
+            monkeypatch.delenv(name, raising=False)
+        else:
+            monkeypatch.setenv(name, value)
+
+    E = 1000
+    for force_generic in (False, True):
+        for small_off in (False, True):
+            switch('AMPCONV_FORCE_GENERIC', '1' if force_generic else None)
+            switch('AMPCONV_SMALL', '0' if small_off else None)
+            for L in (1, 4, 13, 16, 17, 20, 21, 40, 64, 65):
+                for dh in (3, 8, 16, 32, 50, 64, 66):
+                    for H in (1, 2, 8):
+                        for code in (_lib.AMPCONV_F32, _lib.AMPCONV_BF16):
+                            got = lib.ampconv_softmax_stats_bytes(E, L, dh * H, H, code)
+                            want = expected(E, L, dh * H, H, code == _lib.AMPCONV_BF16, force_generic, small_off)
+                            assert got == want, (L, dh, H, code, force_generic, small_off)
+    # the checked example shapes; no buffer for no edges or an invalid shape
+    switch('AMPCONV_FORCE_GENERIC', None)
+    switch('AMPCONV_SMALL', None)
+    assert lib.ampconv_softmax_stats_bytes(E, 20, 256, 8, _lib.AMPCONV_F32) == E * 8 * 40 * 4
+    for code in (_lib.AMPCONV_F32, _lib.AMPCONV_BF16):
+        assert lib.ampconv_softmax_stats_bytes(E, 40, 100, 2, code) == E * 2 * 96 * 4
+    assert lib.ampconv_softmax_stats_bytes(E, 4, 64, 8, _lib.AMPCONV_F32) == 0
+    assert lib.ampconv_softmax_stats_bytes(E, 4, 64, 8, _lib.AMPCONV_BF16) == E * 8 * 32 * 4
+    assert lib.ampconv_softmax_stats_bytes(0, 20, 256, 8, _lib.AMPCONV_F32) == 0
+    assert lib.ampconv_softmax_stats_bytes(E, 20, 250, 8, _lib.AMPCONV_F32) == 0
+    assert lib.ampconv_softmax_stats_bytes(E, 20, 256, 8, 7) == 0
+
+
 def test_long_segment_chunk_follows_the_graph_size(monkeypatch):
     """64 edges per chunk on small graphs (a chunk is one wave's serial walk), 128 from a million edges up
     (DESIGN.md section 5); AMPCONV_HUB_CHUNK pins it."""
