@@ -13,6 +13,7 @@ from .module import AMPGCN, FeatureTokens
 from .sampler import GraphSAINTRandomWalkSampler
 from .partitioned import NodePartition, PartitionedAMPConv
 from .graphed import GraphedAMPConv
+from .heatmap import AttentionHeatmap, top_features
 
 __all__ = ['AMPConv', 'InvalidConfiguration', 'EdgeCSR', 'graph_cache', 'distributed', 'AMPGCN', 'FeatureTokens',
-           'GraphSAINTRandomWalkSampler', 'NodePartition', 'PartitionedAMPConv', 'GraphedAMPConv']
+           'GraphSAINTRandomWalkSampler', 'NodePartition', 'PartitionedAMPConv', 'GraphedAMPConv', 'AttentionHeatmap', 'top_features']

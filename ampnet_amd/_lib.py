@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('AMPCONV_LIB_PATH', os.path.join(_HERE, 'libampconv.so'))   # override: dev A/B builds
 
-EXPECTED_ABI = 107          # AMPCONV_VERSION of include/ampconv.h this binding was written against
+EXPECTED_ABI = 108          # AMPCONV_VERSION of include/ampconv.h this binding was written against
 
 AMPCONV_F32 = 0
 AMPCONV_BF16 = 1
@@ -58,6 +58,9 @@ SIGNATURES = {
                                     View, View, _vp, _i64, _vp, _vp, _vp, _i32, _vp]),
     'ampconv_attn_weights': (_i32, [View, View, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp]),
     'ampconv_attn_scores': (_i32, [View, View, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp]),
+    'ampconv_attn_heatmap': (_i32, [View, View, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64,
+                                    _i32, _vp]),
+    'ampconv_attn_heatmap_shift': (_i32, []),
     'ampconv_gather_segment_sum': (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _vp, _vp]),
     'ampconv_linear_outer': (_i32, [View, View, _i64, _i32, _i32, _i32, ctypes.c_float, _vp, _vp]),
     'ampconv_linear_apply': (_i32, [View, _vp, _i32, _i64, _i32, _i32, _i32, ctypes.c_float, View, _vp]),

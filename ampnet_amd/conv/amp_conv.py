@@ -265,6 +265,17 @@ class AMPConv(MessagePassing):
                                                 m.out_proj.weight.float().t()).view(E, L, D)
         return self._attn_output
 
+    def attention_heatmap(self, token_features, src_features=None, dst_features=None, *, num_features=None,
+                          **selection):
+        """[rows, cols] float64 feature-to-feature heatmap of the last forward pass: the mean attention weight between
+        tokens of source feature `src_features[r]` and destination feature `dst_features[c]` over the selected edges
+        (the reference's calculate_attn_heatmap, visualize_cora_attn_coeffs.py:212-216) -- one
+        heatmap.AttentionHeatmap.update followed by .result(); `selection`: edge_mask / node_class, src_class,
+        dst_class.  Accumulated on the GPU without forming attn_output_weights."""
+        from ..heatmap import AttentionHeatmap
+        return AttentionHeatmap(src_features, dst_features, num_features).update(self, token_features,
+                                                                                 **selection).result()
+
     def _linear_attn_output(self, edge_index, L):
         """Per-edge output of the softmax-free variant, [E, L, D]: Q_d (K_s^T V_s) / sqrt(dh), then the
         out-projection (a diagnostic for small graphs, like the reference's E-sized attribute)."""

@@ -182,3 +182,16 @@ class AMPGCN(nn.Module):
         x = x.mean(dim=1) if self.average_pooling_flag else x[:, 0]      # token mean / token 0 (amp_gcn.py:268-271)
         x = self.final_linear_out(x)
         return F.log_softmax(x, dim=1) if self.softmax_out else self.act_out(x)
+
+    def attention_heatmap(self, layer='conv1', src_features=None, dst_features=None, *, num_features=None,
+                          **selection):
+        """Feature-to-feature attention heatmap of `layer` ('conv1' / 'conv2') for the last forward pass, with this
+        model's own sampled_node_feat_indices: what experiments/visualize_cora_attn_coeffs.py:212-216 computes by hand
+        (AMPConv.attention_heatmap; `selection`: edge_mask / node_class, src_class, dst_class)."""
+        if self.sampled_node_feat_indices is None:
+            raise RuntimeError('attention_heatmap needs the sampled feature indices of a forward pass '
+                               '(downsample_feature_vectors=True)')
+        if src_features is None and num_features is None:
+            num_features = self.num_node_features
+        return getattr(self, layer).attention_heatmap(self.sampled_node_feat_indices, src_features, dst_features,
+                                                      num_features=num_features, **selection)

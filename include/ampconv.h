@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define AMPCONV_VERSION 107
+#define AMPCONV_VERSION 108
 
 enum {
   AMPCONV_OK = 0,
@@ -263,6 +263,29 @@ int ampconv_attn_weights(ampconv_view_t Q, ampconv_view_t K,
 int ampconv_attn_scores(ampconv_view_t Q, ampconv_view_t K,
                         const int64_t *edge_index, int64_t E, int L, int D,
                         int H, float *W, int dtype, void *stream);
+
+/* attn_heatmap: the feature-to-feature attention table of the reference's experiments/visualize_cora_attn_coeffs.py
+ * (calculate_attn_heatmap, :212-216), accumulated without ever forming attn_weights' [E, L, L].  For every selected
+ * edge e = (s -> d), destination token i and source token j with r = rowpos[s, j] >= 0 and c = colpos[d, i] >= 0:
+ *     sum[r, c] += rint(W[e, i, j] * 2^AMPCONV_HEATMAP_SHIFT);   cnt[r, c] += 1
+ * with W the head-mean softmax weight of ampconv_attn_weights.  INDEX CONVENTION, as in the reference: ROW = feature
+ * of the SOURCE token, COLUMN = feature of the DESTINATION token; heat = sum / 2^SHIFT / cnt (0 where cnt == 0).
+ * rowpos / colpos [N, L] int32: position of each token's feature among the selected source / destination features,
+ * -1 (or anything outside [0, rows) / [0, cols)) = not selected.  A feature id that a node holds twice counts once per
+ * token.  edge_mask [E] bytes or NULL (all edges); edges with a node id outside [0, N) are ignored.  sum / cnt
+ * [rows, cols] int64, 8-byte aligned, ACCUMULATED INTO: the caller zeroes them.  Integer adds (vector atomics): the
+ * tables are bitwise independent of launch order and of how the edges are split over calls.  Per-term error
+ * <= 2^-(SHIFT+1).  prior_triples: the (edge, i, j) triples the tables may already hold; a call that could take a cell
+ * past INT64_MAX (prior_triples + E L^2 > AMPCONV_HEATMAP_MAX_TRIPLES) returns AMPCONV_E_BADARG.  E == 0 is OK.
+ * dtype: AMPCONV_F32 views only (else AMPCONV_E_DTYPE).  Tables of at most 4096 cells are accumulated per workgroup in
+ * LDS and flushed once; AMPCONV_HEATMAP_GLOBAL=1 in the environment pins the direct global accumulation.  */
+#define AMPCONV_HEATMAP_SHIFT 28
+#define AMPCONV_HEATMAP_MAX_TRIPLES ((((int64_t)1) << (63 - AMPCONV_HEATMAP_SHIFT)) - 1)
+int ampconv_attn_heatmap(ampconv_view_t Q, ampconv_view_t K, const int64_t *edge_index, int64_t E,
+                         int64_t N, const uint8_t *edge_mask, const int32_t *rowpos,
+                         const int32_t *colpos, int L, int D, int H, int rows, int cols, int64_t *sum,
+                         int64_t *cnt, int64_t prior_triples, int dtype, void *stream);
+int ampconv_attn_heatmap_shift(void);   /* AMPCONV_HEATMAP_SHIFT of the loaded build */
 
 /* ---- node-side helpers --------------------------------------------------------
  * segment_mean: PyG aggr='mean' on an [E, F] message matrix (amp_conv.py:11,
