@@ -14,6 +14,8 @@ from .sampler import GraphSAINTRandomWalkSampler
 from .partitioned import NodePartition, PartitionedAMPConv
 from .graphed import GraphedAMPConv
 from .heatmap import AttentionHeatmap, top_features
+from .glue import ActDropout, TokenReadout, act_dropout, act_dropout_pool
 
 __all__ = ['AMPConv', 'InvalidConfiguration', 'EdgeCSR', 'graph_cache', 'distributed', 'AMPGCN', 'FeatureTokens',
-           'GraphSAINTRandomWalkSampler', 'NodePartition', 'PartitionedAMPConv', 'GraphedAMPConv', 'AttentionHeatmap', 'top_features']
+           'GraphSAINTRandomWalkSampler', 'NodePartition', 'PartitionedAMPConv', 'GraphedAMPConv', 'AttentionHeatmap', 'top_features',
+           'ActDropout', 'TokenReadout', 'act_dropout', 'act_dropout_pool']

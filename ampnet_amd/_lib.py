@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('AMPCONV_LIB_PATH', os.path.join(_HERE, 'libampconv.so'))   # override: dev A/B builds
 
-EXPECTED_ABI = 108          # AMPCONV_VERSION of include/ampconv.h this binding was written against
+EXPECTED_ABI = 109          # AMPCONV_VERSION of include/ampconv.h this binding was written against
 
 AMPCONV_F32 = 0
 AMPCONV_BF16 = 1
@@ -107,6 +107,12 @@ SIGNATURES = {
     'ampconv_segment_mean': (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     'ampconv_mask_rows': (_i32, [_vp, _vp, _i64, _i64, _i32, _vp]),
     'ampconv_masked_colsum': (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp]),
+    'ampconv_act_dropout_fwd': (_i32, [_vp, _i64, _i32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_float, _vp, _i32, _vp]),
+    'ampconv_act_dropout_bwd': (_i32, [_vp, _vp, _i64, _i32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_float, _vp, _i32, _vp]),
+    'ampconv_pool_fwd': (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_float, _vp, _i32,
+                                _vp]),
+    'ampconv_pool_bwd': (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_float, _vp,
+                                _i32, _vp]),
 }
 
 _lib = None

@@ -11,6 +11,14 @@ static inline int ampconv_launch_status() {
   return e == hipSuccess ? AMPCONV_OK : (int)e;
 }
 
+// counter-based generator of the sampler, the featuriser and the dropout mask (include/ampconv.h, "THE MASK")
+__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
 static inline bool view_ok(const ampconv_view_t &v) { return v.ptr != nullptr; }
 
 // element address of (node n, token l, head h) channel 0

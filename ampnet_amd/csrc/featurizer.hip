@@ -12,13 +12,6 @@
 
 namespace {
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
 // one thread per feature column: mean and 1/std (population variance, constant columns -> scale 1,
 // sklearn StandardScaler semantics), double accumulation
 __global__ void zscore_stats_kernel(const float *__restrict__ x, int64_t N, int64_t F,

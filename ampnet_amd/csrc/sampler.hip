@@ -15,13 +15,6 @@
 
 namespace {
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
 // one thread per walk: walks[b, 0] = start[b]; step t picks a uniform out-neighbour of the current
 // node (CSC by source: cscptr/crow), or stays if it has none
 __global__ void random_walk_kernel(const int32_t *__restrict__ cscptr, const int32_t *__restrict__ crow,

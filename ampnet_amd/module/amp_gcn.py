@@ -3,7 +3,7 @@
 Mirrors reference src/ampnet/module/amp_gcn.py:20-118 (constructor arguments, sub-module names and
 therefore state-dict keys: feature_embedding_table, conv1, conv2, final_linear_out) and :239-276
 (forward: dropout_adj -> featurise -> conv1 -> ReLU -> conv2 -> ReLU -> token pooling -> Linear
--> log_softmax).  Both featuriser branches of :120-183 are here: down-sampling of the present features
+-> log_softmax; `fused_glue=True` runs the dropouts, activations and the pooling between those as fused HIP passes).  Both featuriser branches of :120-183 are here: down-sampling of the present features
 (:127-153, the Cora harness) and the full-width branch (:170-181, `downsample_feature_vectors=False`,
 the XOR harness of synthetic_benchmark/xor_training_utils.py:58-72); both poolings of :268-271 (token mean,
 or token 0 with `average_pooling_flag=False`).  Out of scope and not reproduced: the matplotlib/seaborn
@@ -18,6 +18,7 @@ import torch.nn.functional as F
 
 from .. import _lib
 from ..conv import AMPConv
+from ..glue import ActDropout, TokenReadout
 from ..graph import _stream
 
 
@@ -124,7 +125,7 @@ class AMPGCN(nn.Module):
     def __init__(self, device="cuda", embedding_dim=100, num_heads=2, num_node_features=1433,
                  num_sampled_vectors=40, output_dim=7, softmax_out=True, feat_emb_dim=99, val_emb_dim=1,
                  downsample_feature_vectors=True, average_pooling_flag=True, dropout_rate=0.1,
-                 dropout_adj_rate=0.1, feature_repeats=5, seed=0):
+                 dropout_adj_rate=0.1, feature_repeats=5, seed=0, fused_glue=False):
         super().__init__()
         assert embedding_dim == feat_emb_dim + val_emb_dim, \
             "Feature and value dimensions do not add up to total embedding dimension"
@@ -158,6 +159,13 @@ class AMPGCN(nn.Module):
         self.final_linear_out = nn.Linear(in_features=embedding_dim, out_features=output_dim)
         self.drop3 = nn.Dropout(p=dropout_rate)
         self.act_out = nn.Sigmoid()
+        # fused_glue: drop1, ReLU -> drop2 and ReLU -> drop3 -> pooling as one HIP pass each (ampnet_amd/glue.py), masks from
+        # this library's seeded stream instead of torch's.  Kept in a list like _tokens: the sites have no parameters and
+        # the state dict stays the reference's.  Off (the default): the PyTorch ops below, torch's random stream.
+        self.fused_glue = bool(fused_glue)
+        self._glue = [ActDropout(dropout_rate, 'identity', seed, site=1), ActDropout(dropout_rate, 'relu', seed, site=2),
+                      TokenReadout(embedding_dim, dropout_rate, 'relu', 'mean' if average_pooling_flag else 'token0',
+                                   seed, site=3)] if self.fused_glue else []
 
     def forward(self, data, feature_indices=None):
         x, edge_index = data.x.to(self.device), data.edge_index.to(self.device)
@@ -169,6 +177,16 @@ class AMPGCN(nn.Module):
         else:
             x, sampled = self._tokens[0].forward_all(x, self.feature_repeats)
         self.sampled_node_feat_indices = sampled
+        if self.fused_glue:
+            for site in self._glue:
+                site.train(self.training)
+            drop1, relu_drop2, readout = self._glue
+            x = self.conv1(drop1(x), edge_index)
+            self.conv1_embedding = x
+            x = self.conv2(relu_drop2(x), edge_index)
+            self.conv2_embedding = x
+            x = self.final_linear_out(readout(x))
+            return F.log_softmax(x, dim=1) if self.softmax_out else self.act_out(x)
         x = self.drop1(x)
         x = self.conv1(x, edge_index)
         self.conv1_embedding = x

@@ -4,7 +4,7 @@ MI355X path, on a synthetic Cora-shaped graph (Cora itself is a network download
 AMPGCN(D=128, H=4, L=20) + GraphSAINT random-walk batches + Adam + cosine warm restarts +
 node_norm-weighted NLL.  Everything between the data and the loss runs on the GPU.
 
-    python examples/train_graphsaint.py [--epochs 3]
+    python examples/train_graphsaint.py [--epochs 3] [--dropout 0.1 --fused-glue]
 """
 import argparse
 import os
@@ -48,14 +48,18 @@ def main():
                     help="AMPGCN's class defaults (src/ampnet/module/amp_gcn.py:21-35: embedding_dim=100, heads=2, 40 sampled "
                          "vectors: what experiments/cora_benchmark_graphsaint_distributed.py:58 instantiates) instead of the "
                          "128 / 4 / 20 of experiments/cora_benchmark_graphsaint.py")
+    ap.add_argument('--dropout', type=float, default=0.0, metavar='P',
+                    help='dropout_rate of the model (the reference trains with 0.1, amp_gcn.py:31)')
+    ap.add_argument('--fused-glue', action='store_true',
+                    help='dropout, ReLU and token pooling around the layers as fused HIP passes (AMPGCN(fused_glue=True))')
     args = ap.parse_args()
     device = torch.device('cuda:0')
     torch.manual_seed(1)
     data = synthetic_cora(device)
     D, H, L = (100, 2, 40) if args.class_defaults else (128, 4, 20)
     model = AMPGCN(device=device, embedding_dim=D, num_heads=H, num_node_features=1433, num_sampled_vectors=L,
-                   output_dim=7, softmax_out=True, feat_emb_dim=D - 1, val_emb_dim=1, dropout_rate=0.0,
-                   dropout_adj_rate=0.0).to(device)
+                   output_dim=7, softmax_out=True, feat_emb_dim=D - 1, val_emb_dim=1, dropout_rate=args.dropout,
+                   dropout_adj_rate=0.0, fused_glue=args.fused_glue).to(device)
     loader = GraphSAINTRandomWalkSampler(data, batch_size=8, walk_length=150, num_steps=args.steps,
                                          sample_coverage=20, seed=1)
     opt = torch.optim.Adam(model.parameters(), lr=0.005, weight_decay=1e-4)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define AMPCONV_VERSION 108
+#define AMPCONV_VERSION 109
 
 enum {
   AMPCONV_OK = 0,
@@ -475,6 +475,46 @@ int ampconv_feat_build(const float *x, const float *mean, const float *inv_std, 
                        const float *table, int64_t N, int F, int L, int De, float *out, void *stream);
 int ampconv_feat_table_grad(const float *dout, const int32_t *idx, int64_t N, int L, int De, int F,
                             float *dtable, void *stream);
+
+/* ---- glue around the layers: activation, dropout, token pooling (csrc/glue.hip, ABI 109) ------------------------
+ * Reference src/ampnet/module/amp_gcn.py:239-276: drop1 -> conv1 -> ReLU -> drop2 -> conv2 -> ReLU -> drop3 -> token
+ * pooling (:268-271: mean over the L tokens, or token 0); amp_net_classifier_Rahul.py:45-57: the same with ELU.  Each
+ * site is ONE pass over the [N, L*D] tensor, and no dropout mask is ever stored: both passes regenerate it.
+ *
+ * THE MASK (a contract: tests rebuild it on the host, tests/glue_reference.py).  Let i be the flat row-major index of
+ * an element of the logical [N, L*D] tensor and
+ *     splitmix64(x):  x += 0x9E3779B97F4A7C15;  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;
+ *                     x = (x ^ (x >> 27)) * 0x94D049BB133111EB;  return x ^ (x >> 31)        (64-bit, wrapping)
+ *     g = i >> 2;   h = splitmix64(seed ^ splitmix64(g));   f = (h >> (16 * (i & 3))) & 0xFFFF
+ * The element is KEPT iff f >= threshold.  The caller passes threshold = round(p * 65536) <= 65535 (else
+ * AMPCONV_E_BADARG) and scale = 65536 / (65536 - threshold) as a float: the inverse of the EFFECTIVE keep probability,
+ * so E[keep * scale] = 1 exactly.  One hash serves four elements on purpose (a 64-bit hash per element would cost more
+ * vector instructions than the chip has per byte streamed from HBM).  The mask depends on (seed, i) only: it is the
+ * same for every dtype, vector width and launch shape.  threshold = 0 keeps everything; with scale = 1 the result is
+ * then bit-identical to the activation alone.
+ *
+ * act: AMPCONV_ACT_IDENTITY, _RELU, _ELU (alpha = 1).  dtype: AMPCONV_F32 or AMPCONV_BF16 = the storage of every tensor
+ * of the call; arithmetic is fp32.  Tensors are contiguous.  16-byte aligned bases with n (act_dropout) or D (pool) a
+ * multiple of 16 bytes are streamed in 16-byte pieces; anything else (the XOR toy's L = 2, D = 3) runs element-wise.
+ *   act_dropout_fwd: y[i] = keep(i) ? act(x[i]) * scale : 0                                     n elements
+ *   act_dropout_bwd: dx[i] = keep(i) ? dy[i] * scale * act'(x[i]) : 0, act' taken from the saved OUTPUT y (ReLU: y > 0;
+ *                    ELU: a = y / scale, a > 0 ? 1 : a + 1; identity: 1 and y may be NULL) -- y is what the next layer
+ *                    saves as its input anyway, so the site adds no saved tensor
+ *   pool_fwd:        pooled[n, c] = (1 / L) sum_l keep * act(x[n, l, c]) * scale (AMPCONV_POOL_MEAN), or the l = 0 term
+ *                    alone (AMPCONV_POOL_TOKEN0); x [N, L, D], pooled [N, D]; one fp32 chain per output in ascending l,
+ *                    no atomics: bitwise reproducible
+ *   pool_bwd:        dx[n, l, c] = act'(x[n, l, c]) * keep * scale * dpooled[n, c] / L; token 0: without the 1 / L and
+ *                    rows l > 0 are written as exact zeros.  x is the input of pool_fwd (identity: may be NULL).  */
+enum { AMPCONV_ACT_IDENTITY = 0, AMPCONV_ACT_RELU = 1, AMPCONV_ACT_ELU = 2 };
+enum { AMPCONV_POOL_MEAN = 0, AMPCONV_POOL_TOKEN0 = 1 };
+int ampconv_act_dropout_fwd(const void *x, int64_t n, int act, uint64_t seed, uint32_t threshold,
+                            float scale, void *y, int dtype, void *stream);
+int ampconv_act_dropout_bwd(const void *dy, const void *y, int64_t n, int act, uint64_t seed,
+                            uint32_t threshold, float scale, void *dx, int dtype, void *stream);
+int ampconv_pool_fwd(const void *x, int64_t N, int L, int D, int act, int pooling, uint64_t seed,
+                     uint32_t threshold, float scale, void *pooled, int dtype, void *stream);
+int ampconv_pool_bwd(const void *x, const void *dpooled, int64_t N, int L, int D, int act, int pooling,
+                     uint64_t seed, uint32_t threshold, float scale, void *dx, int dtype, void *stream);
 
 #ifdef __cplusplus
 }
