@@ -15,7 +15,8 @@ from .partitioned import NodePartition, PartitionedAMPConv
 from .graphed import GraphedAMPConv
 from .heatmap import AttentionHeatmap, top_features
 from .glue import ActDropout, TokenReadout, act_dropout, act_dropout_pool
+from .head import HeadMetrics, classifier_head, saint_nll_loss
 
 __all__ = ['AMPConv', 'InvalidConfiguration', 'EdgeCSR', 'graph_cache', 'distributed', 'AMPGCN', 'FeatureTokens',
            'GraphSAINTRandomWalkSampler', 'NodePartition', 'PartitionedAMPConv', 'GraphedAMPConv', 'AttentionHeatmap', 'top_features',
-           'ActDropout', 'TokenReadout', 'act_dropout', 'act_dropout_pool']
+           'ActDropout', 'TokenReadout', 'act_dropout', 'act_dropout_pool', 'HeadMetrics', 'classifier_head', 'saint_nll_loss']

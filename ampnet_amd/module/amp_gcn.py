@@ -3,7 +3,8 @@
 Mirrors reference src/ampnet/module/amp_gcn.py:20-118 (constructor arguments, sub-module names and
 therefore state-dict keys: feature_embedding_table, conv1, conv2, final_linear_out) and :239-276
 (forward: dropout_adj -> featurise -> conv1 -> ReLU -> conv2 -> ReLU -> token pooling -> Linear
--> log_softmax; `fused_glue=True` runs the dropouts, activations and the pooling between those as fused HIP passes).  Both featuriser branches of :120-183 are here: down-sampling of the present features
+-> log_softmax; `fused_glue=True` runs the dropouts, activations and the pooling between those as fused HIP passes,
+`fused_head=True` the Linear and the log_softmax / sigmoid as one more, and `nll_loss` the training loss behind them).  Both featuriser branches of :120-183 are here: down-sampling of the present features
 (:127-153, the Cora harness) and the full-width branch (:170-181, `downsample_feature_vectors=False`,
 the XOR harness of synthetic_benchmark/xor_training_utils.py:58-72); both poolings of :268-271 (token mean,
 or token 0 with `average_pooling_flag=False`).  Out of scope and not reproduced: the matplotlib/seaborn
@@ -19,6 +20,7 @@ import torch.nn.functional as F
 from .. import _lib
 from ..conv import AMPConv
 from ..glue import ActDropout, TokenReadout
+from ..head import MAX_CLASSES, classifier_head, saint_nll_loss
 from ..graph import _stream
 
 
@@ -125,7 +127,7 @@ class AMPGCN(nn.Module):
     def __init__(self, device="cuda", embedding_dim=100, num_heads=2, num_node_features=1433,
                  num_sampled_vectors=40, output_dim=7, softmax_out=True, feat_emb_dim=99, val_emb_dim=1,
                  downsample_feature_vectors=True, average_pooling_flag=True, dropout_rate=0.1,
-                 dropout_adj_rate=0.1, feature_repeats=5, seed=0, fused_glue=False):
+                 dropout_adj_rate=0.1, feature_repeats=5, seed=0, fused_glue=False, fused_head=False):
         super().__init__()
         assert embedding_dim == feat_emb_dim + val_emb_dim, \
             "Feature and value dimensions do not add up to total embedding dimension"
@@ -166,8 +168,61 @@ class AMPGCN(nn.Module):
         self._glue = [ActDropout(dropout_rate, 'identity', seed, site=1), ActDropout(dropout_rate, 'relu', seed, site=2),
                       TokenReadout(embedding_dim, dropout_rate, 'relu', 'mean' if average_pooling_flag else 'token0',
                                    seed, site=3)] if self.fused_glue else []
+        # fused_head: final_linear_out -> log_softmax / sigmoid as one HIP kernel per direction on the module's own weight
+        # and bias (ampnet_amd/head.py); nll_loss() below fuses the loss and its metrics behind it as well.
+        self.fused_head = bool(fused_head)
+        if self.fused_head and output_dim > MAX_CLASSES:
+            raise ValueError(f'fused_head supports output_dim <= {MAX_CLASSES}, got {output_dim}')
+
+    def _pooled(self, data, feature_indices=None):
+        """forward() up to the token pooling: [N, embedding_dim], the input of final_linear_out."""
+        x, edge_index = data.x.to(self.device), data.edge_index.to(self.device)
+        if self.training and self.dropout_adj_rate > 0:                       # dropout_adj (amp_gcn.py:241)
+            keep = torch.rand(edge_index.size(1), device=edge_index.device) >= self.dropout_adj_rate
+            edge_index = edge_index[:, keep]
+        if self.downsampling_vectors:
+            x, sampled = self._tokens[0](x, feature_indices)
+        else:
+            x, sampled = self._tokens[0].forward_all(x, self.feature_repeats)
+        self.sampled_node_feat_indices = sampled
+        if self.fused_glue:
+            for site in self._glue:
+                site.train(self.training)
+            drop1, relu_drop2, readout = self._glue
+            x = self.conv1(drop1(x), edge_index)
+            self.conv1_embedding = x
+            x = self.conv2(relu_drop2(x), edge_index)
+            self.conv2_embedding = x
+            return readout(x)
+        x = self.conv1(self.drop1(x), edge_index)
+        self.conv1_embedding = x
+        x = self.conv2(self.drop2(F.relu(x)), edge_index)
+        self.conv2_embedding = x
+        x = self.drop3(F.relu(x))
+        x = x.reshape(x.shape[0], x.shape[1] // self.emb_dim, self.emb_dim)
+        return x.mean(dim=1) if self.average_pooling_flag else x[:, 0]
+
+    def nll_loss(self, data, y=None, node_norm=None, masks=None, grad_mask=0, metrics=None, feature_indices=None):
+        """The reference's training loss (F.nll_loss(model(data), y, reduction='none') * node_norm)[masks[grad_mask]].sum()
+        with the head, the loss and the metrics of every mask fused into one kernel per direction and no device
+        synchronisation (ampnet_amd.saint_nll_loss; `metrics`: a HeadMetrics).  y and node_norm default to data.y and
+        data.node_norm (no weights if the batch has none).  Sets conv1_embedding, conv2_embedding and
+        sampled_node_feat_indices as forward does.  Needs softmax_out=True: there is no fused loss for the sigmoid."""
+        if not self.softmax_out:
+            raise ValueError('nll_loss needs softmax_out=True (no fused loss for the sigmoid output)')
+        if y is None:
+            y = data.y
+        if node_norm is None:
+            node_norm = getattr(data, 'node_norm', None)
+        pooled = self._pooled(data, feature_indices)
+        y = y.to(self.device)
+        return saint_nll_loss(pooled, self.final_linear_out.weight, self.final_linear_out.bias, y,
+                              None if node_norm is None else node_norm.to(self.device), masks, grad_mask, metrics)
 
     def forward(self, data, feature_indices=None):
+        if self.fused_head:
+            return classifier_head(self._pooled(data, feature_indices), self.final_linear_out.weight,
+                                   self.final_linear_out.bias, 'log_softmax' if self.softmax_out else 'sigmoid')
         x, edge_index = data.x.to(self.device), data.edge_index.to(self.device)
         if self.training and self.dropout_adj_rate > 0:                       # dropout_adj (amp_gcn.py:241)
             keep = torch.rand(edge_index.size(1), device=edge_index.device) >= self.dropout_adj_rate

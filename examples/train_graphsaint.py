@@ -4,7 +4,7 @@ MI355X path, on a synthetic Cora-shaped graph (Cora itself is a network download
 AMPGCN(D=128, H=4, L=20) + GraphSAINT random-walk batches + Adam + cosine warm restarts +
 node_norm-weighted NLL.  Everything between the data and the loss runs on the GPU.
 
-    python examples/train_graphsaint.py [--epochs 3] [--dropout 0.1 --fused-glue]
+    python examples/train_graphsaint.py [--epochs 3] [--dropout 0.1 --fused-glue] [--fused-head]
 """
 import argparse
 import os
@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
-from ampnet_amd import AMPGCN, GraphSAINTRandomWalkSampler  # noqa: E402
+from ampnet_amd import AMPGCN, GraphSAINTRandomWalkSampler, HeadMetrics  # noqa: E402
 
 
 def synthetic_cora(device, n=2708, f=1433, classes=7, seed=1):
@@ -52,6 +52,9 @@ def main():
                     help='dropout_rate of the model (the reference trains with 0.1, amp_gcn.py:31)')
     ap.add_argument('--fused-glue', action='store_true',
                     help='dropout, ReLU and token pooling around the layers as fused HIP passes (AMPGCN(fused_glue=True))')
+    ap.add_argument('--fused-head', action='store_true',
+                    help='Linear + log_softmax + node_norm-weighted NLL + train / test metrics as one HIP kernel per '
+                         'direction (AMPGCN(fused_head=True).nll_loss): no read-back per step, one per epoch')
     args = ap.parse_args()
     device = torch.device('cuda:0')
     torch.manual_seed(1)
@@ -59,30 +62,46 @@ def main():
     D, H, L = (100, 2, 40) if args.class_defaults else (128, 4, 20)
     model = AMPGCN(device=device, embedding_dim=D, num_heads=H, num_node_features=1433, num_sampled_vectors=L,
                    output_dim=7, softmax_out=True, feat_emb_dim=D - 1, val_emb_dim=1, dropout_rate=args.dropout,
-                   dropout_adj_rate=0.0, fused_glue=args.fused_glue).to(device)
+                   dropout_adj_rate=0.0, fused_glue=args.fused_glue, fused_head=args.fused_head).to(device)
     loader = GraphSAINTRandomWalkSampler(data, batch_size=8, walk_length=150, num_steps=args.steps,
                                          sample_coverage=20, seed=1)
     opt = torch.optim.Adam(model.parameters(), lr=0.005, weight_decay=1e-4)
     sched = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(opt, T_0=400, T_mult=2)
     t0 = time.time()
     history = []
+    metrics = HeadMetrics(2, device) if args.fused_head else None
     for epoch in range(args.epochs):
         tot = cnt = correct = 0
         torch.cuda.synchronize()
         te = time.time()
-        for batch in loader:
-            model.train()
-            opt.zero_grad()
-            out = model(batch)
-            loss = (F.nll_loss(out, batch.y, reduction='none') * batch.node_norm)[batch.train_mask].sum()
-            loss.backward()
-            opt.step()
-            sched.step()
-            tot += loss.item(); cnt += 1
-            correct += float((out.argmax(1) == batch.y)[batch.train_mask].float().mean())
+        if args.fused_head:
+            metrics.zero_()
+            for batch in loader:
+                model.train()
+                opt.zero_grad()
+                model.nll_loss(batch, masks=(batch.train_mask, batch.test_mask), metrics=metrics).backward()
+                opt.step()
+                sched.step()
+                cnt += 1
+            m = metrics.read()                                              # the epoch's one read-back
+            tot, correct = m['loss_sum'][0], cnt * m['correct'][0] / max(m['count'][0], 1)    # accuracy over the epoch's nodes
+            extra = (f'  test loss {m["loss_sum"][1] / cnt:.4f}  test acc {m["correct"][1] / max(m["count"][1], 1):.3f}'
+                     + (f'  ({m["bad_labels"]} labels out of range)' if m['bad_labels'] else ''))
+        else:
+            extra = ''
+            for batch in loader:
+                model.train()
+                opt.zero_grad()
+                out = model(batch)
+                loss = (F.nll_loss(out, batch.y, reduction='none') * batch.node_norm)[batch.train_mask].sum()
+                loss.backward()
+                opt.step()
+                sched.step()
+                tot += loss.item(); cnt += 1
+                correct += float((out.argmax(1) == batch.y)[batch.train_mask].float().mean())
         history.append((tot / cnt, correct / cnt))
         torch.cuda.synchronize()
-        print(f'epoch {epoch}: train loss {tot / cnt:.4f}  train acc {correct / cnt:.3f}  '
+        print(f'epoch {epoch}: train loss {tot / cnt:.4f}  train acc {correct / cnt:.3f}{extra}  '
               f'({time.time() - t0:.1f} s; this epoch {time.time() - te:.3f} s = {1e3 * (time.time() - te) / cnt:.2f} ms '
               f'per sampled batch, sampler + 2 AMPConv layers fwd+bwd + Adam)', flush=True)
     model.eval()

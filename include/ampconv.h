@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define AMPCONV_VERSION 109
+#define AMPCONV_VERSION 110
 
 enum {
   AMPCONV_OK = 0,
@@ -515,6 +515,59 @@ int ampconv_pool_fwd(const void *x, int64_t N, int L, int D, int act, int poolin
                      uint32_t threshold, float scale, void *pooled, int dtype, void *stream);
 int ampconv_pool_bwd(const void *x, const void *dpooled, int64_t N, int L, int D, int act, int pooling,
                      uint64_t seed, uint32_t threshold, float scale, void *dx, int dtype, void *stream);
+
+/* ---- classifier head and GraphSAINT-weighted NLL loss (csrc/head.hip, ABI 110) --------------------------------------
+ * Reference src/ampnet/module/amp_gcn.py:272-276 (final_linear_out, then log_softmax or, with softmax_out=False, the
+ * sigmoid) and experiments/cora_benchmark_graphsaint.py:105-128:
+ *     loss = (F.nll_loss(out, y, reduction='none') * node_norm)[mask].sum();  acc = (out.argmax(1) == y)[mask].mean()
+ * pooled [N, D]: row n starts `stride` elements (>= D) behind row n - 1; dtype AMPCONV_F32 or AMPCONV_BF16 is ITS storage
+ * (and dpooled's, which is contiguous [N, D]).  W [C, D] and b [C] are contiguous fp32, 1 <= C <= AMPCONV_HEAD_MAX_CLASSES,
+ * D >= 1; all arithmetic is fp32.  Rows are read in 16-byte pieces where pooled, W and dpooled are 16-byte aligned and
+ * D and stride are whole pieces, element by element otherwise.  No [N, C] tensor is written except the `out` / `logp`
+ * the caller passes.  C outside 1..64, negative sizes, stride < D, an unknown kind, M outside 1..4 or grad_mask outside
+ * [0, M): AMPCONV_E_BADARG; another dtype: AMPCONV_E_DTYPE; a short workspace: AMPCONV_E_WORKSPACE -- nothing is launched.
+ * N == 0 succeeds: dW and db are written as zeros, the loss as 0, nothing is accumulated.
+ *   head_fwd:  out[n, :] = log_softmax(pooled[n] W^T + b) (kind AMPCONV_HEAD_LOG_SOFTMAX; the row maximum is subtracted
+ *              before exp) or sigmoid(...) (AMPCONV_HEAD_SIGMOID); out [N, C] fp32 contiguous.
+ *   head_bwd:  dz = dout - exp(out) * rowsum(dout) (log_softmax) or dout * out * (1 - out) (sigmoid) from the saved out;
+ *              dpooled = dz W (may be NULL: not wanted), dW = dz^T pooled, db = colsum(dz).
+ *   head_nll_fwd: with logp = log_softmax(pooled W^T + b), labels y [N] int64, weights w [N] fp32 (NULL: 1), masks [M, N]
+ *              bytes (NULL: M == 1, one all-true mask).  Node n is SELECTED by mask m when masks[m, n] != 0 and
+ *              y[n] != AMPCONV_HEAD_IGNORE_INDEX (torch's ignore_index).  A selected node whose label is outside [0, C)
+ *              is never used as an index: it is skipped by every mask and counted once in the bad-labels slot.  Per mask m,
+ *              ADDED to metrics (int64 [AMPCONV_HEAD_METRICS_SLOTS], the caller zeroes it; NULL: not wanted):
+ *                  metrics[3 m]     += sum_n rint(w[n] * -logp[n, y[n]] * 2^AMPCONV_HEAD_LOSS_SHIFT)
+ *                  metrics[3 m + 1] += selected nodes;   metrics[3 m + 2] += those with argmax_c logp[n, c] == y[n]
+ *                  metrics[12]      += bad labels                  (argmax ties: the lowest class, as torch.argmax)
+ *              *loss (fp32, device) = this call's loss sum of mask grad_mask / 2^SHIFT.  logp [N, C] is written if not
+ *              NULL.  scratch: AMPCONV_HEAD_METRICS_SLOTS int64 of the caller's, overwritten (the call's own sums).
+ *   head_nll_bwd: dz[n] = *g * w[n] * [n selected by grad_mask, label in range] * (softmax[n] - onehot(y[n])) with the
+ *              upstream gradient *g read ON THE DEVICE, then dpooled, dW, db as head_bwd.  Rows without a gradient get
+ *              exact zeros written.
+ * DETERMINISM.  Every output has the same bits on every launch.  dW and db: a fixed-order two-stage reduction --
+ * workgroup partials [workgroups, C, D + 1] in `workspace` (ampconv_head_workspace_bytes(N, D, C); need not be zeroed),
+ * added in workgroup order by a second kernel; no floating-point atomics anywhere.  The metric sums: 64-bit integer
+ * atomics, the loss terms in fixed point with AMPCONV_HEAD_LOSS_SHIFT = 32 fraction bits: per-term error <= 2^-33, and a
+ * running |sum| below 2^31 (e.g. 10^6 nodes of weighted loss 2000 each) is exact integer arithmetic.  */
+enum { AMPCONV_HEAD_LOG_SOFTMAX = 0, AMPCONV_HEAD_SIGMOID = 1 };
+#define AMPCONV_HEAD_MAX_CLASSES 64
+#define AMPCONV_HEAD_MAX_MASKS 4
+#define AMPCONV_HEAD_METRICS_SLOTS 13
+#define AMPCONV_HEAD_LOSS_SHIFT 32
+#define AMPCONV_HEAD_IGNORE_INDEX (-100)
+size_t ampconv_head_workspace_bytes(int64_t N, int D, int C);
+int ampconv_head_fwd(const void *pooled, int64_t N, int D, int64_t stride, const float *W, const float *b, int C,
+                     int kind, float *out, int dtype, void *stream);
+int ampconv_head_bwd(const void *pooled, int64_t N, int D, int64_t stride, const float *W, int C, int kind,
+                     const float *dout, const float *out, void *dpooled, float *dW, float *db, void *workspace,
+                     size_t workspace_bytes, int dtype, void *stream);
+int ampconv_head_nll_fwd(const void *pooled, int64_t N, int D, int64_t stride, const float *W, const float *b, int C,
+                         const int64_t *y, const float *w, const uint8_t *masks, int M, int grad_mask, float *logp,
+                         int64_t *metrics, int64_t *scratch, float *loss, int dtype, void *stream);
+int ampconv_head_nll_bwd(const void *pooled, int64_t N, int D, int64_t stride, const float *W, const float *b, int C,
+                         const int64_t *y, const float *w, const uint8_t *masks, int M, int grad_mask, const float *g,
+                         void *dpooled, float *dW, float *db, void *workspace, size_t workspace_bytes, int dtype,
+                         void *stream);
 
 #ifdef __cplusplus
 }
