@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('AMPCONV_LIB_PATH', os.path.join(_HERE, 'libampconv.so'))   # override: dev A/B builds
 
-EXPECTED_ABI = 110          # AMPCONV_VERSION of include/ampconv.h this binding was written against
+EXPECTED_ABI = 111          # AMPCONV_VERSION of include/ampconv.h this binding was written against
 
 AMPCONV_F32 = 0
 AMPCONV_BF16 = 1
@@ -120,6 +120,15 @@ SIGNATURES = {
                                     _i32, _vp]),
     'ampconv_head_nll_bwd': (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
                                     _vp, _sz, _i32, _vp]),
+    'ampconv_norm_workspace_bytes': (_sz, [_i64, _i32]),
+    'ampconv_norm_fwd': (_i32, [_vp, _i64, _i32, _vp, _vp, ctypes.c_float, _i32, ctypes.c_uint64, ctypes.c_uint32,
+                                ctypes.c_float, _vp, _vp, _i32, _vp]),
+    'ampconv_norm_bwd': (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _i32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_float,
+                                _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
+    'ampconv_norm_pool_fwd': (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, ctypes.c_float, _i32, _i32, ctypes.c_uint64,
+                                     ctypes.c_uint32, ctypes.c_float, _vp, _vp, _i32, _vp]),
+    'ampconv_norm_pool_bwd': (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, ctypes.c_uint64, ctypes.c_uint32,
+                                     ctypes.c_float, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
 }
 
 _lib = None

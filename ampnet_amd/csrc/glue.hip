@@ -9,61 +9,12 @@
 // All four operations stream their tensors once: 16 bytes per lane, a wave's lanes on consecutive 16-byte pieces,
 // four loads in flight per lane and stream, no LDS.  Bases that are not 16-byte aligned and rows that are no multiple
 // of 16 bytes (the XOR toy: L = 2, D = 3) take the element-wise kernels at the end of each section.
-#include <type_traits>
-
-#include "common.h"
+#include "site_common.h"
 
 namespace {
 
 constexpr int kUnroll = 4;                      // 16-byte loads in flight per lane and input stream
 constexpr int kMaxBlocks = 2048;                // grid-stride beyond 256 CUs x 8 workgroups
-
-template <typename T>
-struct alignas(16) Piece {
-  static constexpr int N = 16 / sizeof(T);
-  T e[N];
-};
-
-template <int ACT>
-__device__ __forceinline__ float act_value(float x) {
-  if constexpr (ACT == AMPCONV_ACT_RELU) return x > 0.f ? x : 0.f;
-  if constexpr (ACT == AMPCONV_ACT_ELU) return x > 0.f ? x : expm1f(x);
-  return x;
-}
-// act'(x) from a = act(x): what the element-wise backward has (it is handed the saved OUTPUT)
-template <int ACT>
-__device__ __forceinline__ float act_slope_of_value(float a) {
-  if constexpr (ACT == AMPCONV_ACT_RELU) return a > 0.f ? 1.f : 0.f;
-  if constexpr (ACT == AMPCONV_ACT_ELU) return a > 0.f ? 1.f : a + 1.f;
-  return 1.f;
-}
-// act'(x) from x: what the pooling backward has (the layer output is alive anyway)
-template <int ACT>
-__device__ __forceinline__ float act_slope_of_input(float x) {
-  if constexpr (ACT == AMPCONV_ACT_RELU) return x > 0.f ? 1.f : 0.f;
-  if constexpr (ACT == AMPCONV_ACT_ELU) return x > 0.f ? 1.f : expf(x);
-  return 1.f;
-}
-
-// THE MASK (include/ampconv.h): bit k of the result = element 4 g0 + k is kept, for the NP / 4 groups of one piece.
-// thr == 0 keeps everything and costs no hash (wave-uniform branch).
-template <int NP>
-__device__ __forceinline__ uint32_t keep_bits(uint64_t seed, uint32_t thr, uint64_t g0) {
-  if (thr == 0) return 0xFFFFFFFFu;
-  uint32_t bits = 0;
-#pragma unroll
-  for (int j = 0; j < NP / 4; ++j) {
-    const uint64_t h = splitmix64(seed ^ splitmix64(g0 + j));
-#pragma unroll
-    for (int k = 0; k < 4; ++k) bits |= (uint32_t)(((uint32_t)(h >> (16 * k)) & 0xFFFFu) >= thr) << (4 * j + k);
-  }
-  return bits;
-}
-__device__ __forceinline__ bool keep_one(uint64_t seed, uint32_t thr, uint64_t i) {
-  if (thr == 0) return true;
-  const uint64_t h = splitmix64(seed ^ splitmix64(i >> 2));
-  return ((uint32_t)(h >> (16 * (i & 3))) & 0xFFFFu) >= thr;
-}
 
 // ---- activation + dropout, element-wise ----------------------------------------------------------------------------
 template <typename T, int ACT>
@@ -293,25 +244,10 @@ __global__ __launch_bounds__(256) void pool_bwd_scalar(const T *__restrict__ X, 
   for (; l < L; ++l) dX[i0 + (int64_t)l * D] = (T)0.f;
 }
 
-// f(T{}, integral_constant<int, ACT>{}) for the (dtype, activation) of a call
-template <typename F>
-int with_type_and_act(int dtype, int act, const F &f) {
-  if (dtype != AMPCONV_F32 && dtype != AMPCONV_BF16) return AMPCONV_E_DTYPE;
-  if (act < AMPCONV_ACT_IDENTITY || act > AMPCONV_ACT_ELU) return AMPCONV_E_BADARG;
-  auto by_act = [&](auto t) {
-    if (act == AMPCONV_ACT_RELU) return f(t, std::integral_constant<int, AMPCONV_ACT_RELU>{});
-    if (act == AMPCONV_ACT_ELU) return f(t, std::integral_constant<int, AMPCONV_ACT_ELU>{});
-    return f(t, std::integral_constant<int, AMPCONV_ACT_IDENTITY>{});
-  };
-  return dtype == AMPCONV_BF16 ? by_act(__bf16{}) : by_act(float{});
-}
-
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 inline unsigned capped_blocks(int64_t work_items, int64_t per_block) {
   const int64_t b = (work_items + per_block - 1) / per_block;
   return (unsigned)(b < kMaxBlocks ? b : kMaxBlocks);
 }
-inline bool mask_args_ok(uint32_t thr, float scale) { return thr <= 65535u && scale > 0.f; }
 
 }  // namespace
 

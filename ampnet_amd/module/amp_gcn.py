@@ -4,7 +4,8 @@ Mirrors reference src/ampnet/module/amp_gcn.py:20-118 (constructor arguments, su
 therefore state-dict keys: feature_embedding_table, conv1, conv2, final_linear_out) and :239-276
 (forward: dropout_adj -> featurise -> conv1 -> ReLU -> conv2 -> ReLU -> token pooling -> Linear
 -> log_softmax; `fused_glue=True` runs the dropouts, activations and the pooling between those as fused HIP passes,
-`fused_head=True` the Linear and the log_softmax / sigmoid as one more, and `nll_loss` the training loss behind them).  Both featuriser branches of :120-183 are here: down-sampling of the present features
+`fused_head=True` the Linear and the log_softmax / sigmoid as one more, and `nll_loss` the training loss behind them;
+`layer_norm=True` adds the per-token LayerNorm sites norm1, norm2 of experiments/cora_overfit_one_subgraph.py:46-107).  Both featuriser branches of :120-183 are here: down-sampling of the present features
 (:127-153, the Cora harness) and the full-width branch (:170-181, `downsample_feature_vectors=False`,
 the XOR harness of synthetic_benchmark/xor_training_utils.py:58-72); both poolings of :268-271 (token mean,
 or token 0 with `average_pooling_flag=False`).  Out of scope and not reproduced: the matplotlib/seaborn
@@ -21,6 +22,7 @@ from .. import _lib
 from ..conv import AMPConv
 from ..glue import ActDropout, TokenReadout
 from ..head import MAX_CLASSES, classifier_head, saint_nll_loss
+from ..norm import NormTokenReadout, TokenLayerNorm
 from ..graph import _stream
 
 
@@ -127,7 +129,7 @@ class AMPGCN(nn.Module):
     def __init__(self, device="cuda", embedding_dim=100, num_heads=2, num_node_features=1433,
                  num_sampled_vectors=40, output_dim=7, softmax_out=True, feat_emb_dim=99, val_emb_dim=1,
                  downsample_feature_vectors=True, average_pooling_flag=True, dropout_rate=0.1,
-                 dropout_adj_rate=0.1, feature_repeats=5, seed=0, fused_glue=False, fused_head=False):
+                 dropout_adj_rate=0.1, feature_repeats=5, seed=0, fused_glue=False, fused_head=False, layer_norm=False):
         super().__init__()
         assert embedding_dim == feat_emb_dim + val_emb_dim, \
             "Feature and value dimensions do not add up to total embedding dimension"
@@ -165,9 +167,18 @@ class AMPGCN(nn.Module):
         # this library's seeded stream instead of torch's.  Kept in a list like _tokens: the sites have no parameters and
         # the state dict stays the reference's.  Off (the default): the PyTorch ops below, torch's random stream.
         self.fused_glue = bool(fused_glue)
+        pooling = 'mean' if average_pooling_flag else 'token0'
         self._glue = [ActDropout(dropout_rate, 'identity', seed, site=1), ActDropout(dropout_rate, 'relu', seed, site=2),
-                      TokenReadout(embedding_dim, dropout_rate, 'relu', 'mean' if average_pooling_flag else 'token0',
-                                   seed, site=3)] if self.fused_glue else []
+                      TokenReadout(embedding_dim, dropout_rate, 'relu', pooling, seed, site=3)] if self.fused_glue else []
+        # layer_norm: the deeper reference model's per-token nn.LayerNorm behind each layer (experiments/
+        # cora_overfit_one_subgraph.py:46-107, sub-modules norm1, norm2 as there): conv1 -> [norm1 -> ReLU -> drop2] -> conv2
+        # -> [norm2 -> ReLU -> drop3 -> pooling], each bracket ONE HIP pass (ampnet_amd/norm.py) whatever fused_glue says;
+        # their masks are always this library's.  Off (the default): no such sub-modules, the reference class's state dict.
+        self.layer_norm = bool(layer_norm)
+        if self.layer_norm:
+            self.norm1 = TokenLayerNorm(embedding_dim, p=dropout_rate, activation='relu', seed=seed, site=4)
+            self.norm2 = NormTokenReadout(embedding_dim, p=dropout_rate, activation='relu', pooling=pooling, seed=seed,
+                                          site=5)
         # fused_head: final_linear_out -> log_softmax / sigmoid as one HIP kernel per direction on the module's own weight
         # and bias (ampnet_amd/head.py); nll_loss() below fuses the loss and its metrics behind it as well.
         self.fused_head = bool(fused_head)
@@ -185,22 +196,23 @@ class AMPGCN(nn.Module):
         else:
             x, sampled = self._tokens[0].forward_all(x, self.feature_repeats)
         self.sampled_node_feat_indices = sampled
-        if self.fused_glue:
-            for site in self._glue:
-                site.train(self.training)
-            drop1, relu_drop2, readout = self._glue
-            x = self.conv1(drop1(x), edge_index)
-            self.conv1_embedding = x
-            x = self.conv2(relu_drop2(x), edge_index)
-            self.conv2_embedding = x
-            return readout(x)
-        x = self.conv1(self.drop1(x), edge_index)
+        for site in self._glue:
+            site.train(self.training)
+        x = self.conv1(self._glue[0](x) if self.fused_glue else self.drop1(x), edge_index)
         self.conv1_embedding = x
+        if self.layer_norm:                                                   # norm -> ReLU -> dropout (-> pooling): one pass each
+            x = self.conv2(self.norm1(x), edge_index)
+            self.conv2_embedding = x
+            return self.norm2(x)
+        if self.fused_glue:
+            x = self.conv2(self._glue[1](x), edge_index)
+            self.conv2_embedding = x
+            return self._glue[2](x)
         x = self.conv2(self.drop2(F.relu(x)), edge_index)
         self.conv2_embedding = x
         x = self.drop3(F.relu(x))
         x = x.reshape(x.shape[0], x.shape[1] // self.emb_dim, self.emb_dim)
-        return x.mean(dim=1) if self.average_pooling_flag else x[:, 0]
+        return x.mean(dim=1) if self.average_pooling_flag else x[:, 0]      # token mean / token 0 (amp_gcn.py:268-271)
 
     def nll_loss(self, data, y=None, node_norm=None, masks=None, grad_mask=0, metrics=None, feature_indices=None):
         """The reference's training loss (F.nll_loss(model(data), y, reduction='none') * node_norm)[masks[grad_mask]].sum()
@@ -220,39 +232,10 @@ class AMPGCN(nn.Module):
                               None if node_norm is None else node_norm.to(self.device), masks, grad_mask, metrics)
 
     def forward(self, data, feature_indices=None):
+        x = self._pooled(data, feature_indices)
         if self.fused_head:
-            return classifier_head(self._pooled(data, feature_indices), self.final_linear_out.weight,
-                                   self.final_linear_out.bias, 'log_softmax' if self.softmax_out else 'sigmoid')
-        x, edge_index = data.x.to(self.device), data.edge_index.to(self.device)
-        if self.training and self.dropout_adj_rate > 0:                       # dropout_adj (amp_gcn.py:241)
-            keep = torch.rand(edge_index.size(1), device=edge_index.device) >= self.dropout_adj_rate
-            edge_index = edge_index[:, keep]
-        if self.downsampling_vectors:
-            x, sampled = self._tokens[0](x, feature_indices)
-        else:
-            x, sampled = self._tokens[0].forward_all(x, self.feature_repeats)
-        self.sampled_node_feat_indices = sampled
-        if self.fused_glue:
-            for site in self._glue:
-                site.train(self.training)
-            drop1, relu_drop2, readout = self._glue
-            x = self.conv1(drop1(x), edge_index)
-            self.conv1_embedding = x
-            x = self.conv2(relu_drop2(x), edge_index)
-            self.conv2_embedding = x
-            x = self.final_linear_out(readout(x))
-            return F.log_softmax(x, dim=1) if self.softmax_out else self.act_out(x)
-        x = self.drop1(x)
-        x = self.conv1(x, edge_index)
-        self.conv1_embedding = x
-        x = F.relu(x)
-        x = self.drop2(x)
-        x = self.conv2(x, edge_index)
-        self.conv2_embedding = x
-        x = F.relu(x)
-        x = self.drop3(x)
-        x = x.reshape(x.shape[0], x.shape[1] // self.emb_dim, self.emb_dim)
-        x = x.mean(dim=1) if self.average_pooling_flag else x[:, 0]      # token mean / token 0 (amp_gcn.py:268-271)
+            return classifier_head(x, self.final_linear_out.weight, self.final_linear_out.bias,
+                                   'log_softmax' if self.softmax_out else 'sigmoid')
         x = self.final_linear_out(x)
         return F.log_softmax(x, dim=1) if self.softmax_out else self.act_out(x)
 

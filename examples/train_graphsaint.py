@@ -4,7 +4,7 @@ MI355X path, on a synthetic Cora-shaped graph (Cora itself is a network download
 AMPGCN(D=128, H=4, L=20) + GraphSAINT random-walk batches + Adam + cosine warm restarts +
 node_norm-weighted NLL.  Everything between the data and the loss runs on the GPU.
 
-    python examples/train_graphsaint.py [--epochs 3] [--dropout 0.1 --fused-glue] [--fused-head]
+    python examples/train_graphsaint.py [--epochs 3] [--dropout 0.1 --fused-glue] [--fused-head] [--layer-norm]
 """
 import argparse
 import os
@@ -52,6 +52,8 @@ def main():
                     help='dropout_rate of the model (the reference trains with 0.1, amp_gcn.py:31)')
     ap.add_argument('--fused-glue', action='store_true',
                     help='dropout, ReLU and token pooling around the layers as fused HIP passes (AMPGCN(fused_glue=True))')
+    ap.add_argument('--layer-norm', action='store_true',
+                    help='per-token LayerNorm behind each layer, fused with ReLU, dropout and the pooling (AMPGCN(layer_norm=True))')
     ap.add_argument('--fused-head', action='store_true',
                     help='Linear + log_softmax + node_norm-weighted NLL + train / test metrics as one HIP kernel per '
                          'direction (AMPGCN(fused_head=True).nll_loss): no read-back per step, one per epoch')
@@ -62,7 +64,8 @@ def main():
     D, H, L = (100, 2, 40) if args.class_defaults else (128, 4, 20)
     model = AMPGCN(device=device, embedding_dim=D, num_heads=H, num_node_features=1433, num_sampled_vectors=L,
                    output_dim=7, softmax_out=True, feat_emb_dim=D - 1, val_emb_dim=1, dropout_rate=args.dropout,
-                   dropout_adj_rate=0.0, fused_glue=args.fused_glue, fused_head=args.fused_head).to(device)
+                   dropout_adj_rate=0.0, fused_glue=args.fused_glue, fused_head=args.fused_head,
+                   layer_norm=args.layer_norm).to(device)
     loader = GraphSAINTRandomWalkSampler(data, batch_size=8, walk_length=150, num_steps=args.steps,
                                          sample_coverage=20, seed=1)
     opt = torch.optim.Adam(model.parameters(), lr=0.005, weight_decay=1e-4)

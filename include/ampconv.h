@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define AMPCONV_VERSION 110
+#define AMPCONV_VERSION 111
 
 enum {
   AMPCONV_OK = 0,
@@ -568,6 +568,57 @@ int ampconv_head_nll_bwd(const void *pooled, int64_t N, int D, int64_t stride, c
                          const int64_t *y, const float *w, const uint8_t *masks, int M, int grad_mask, const float *g,
                          void *dpooled, float *dW, float *db, void *workspace, size_t workspace_bytes, int dtype,
                          void *stream);
+
+/* ---- per-token LayerNorm sites (csrc/norm.hip, ABI 111) --------------------------------------------------------------
+ * Reference experiments/cora_overfit_one_subgraph.py:46-107: behind each AMPConv layer
+ *     reshape [N, L, D] -> nn.LayerNorm(D) -> ReLU -> reshape back,      the last one followed by the token pooling
+ * (amp_net_classifier_Rahul.py:17 defines the same LayerNorm).  Each site is ONE pass over the [N, L*D] tensor per
+ * direction: the normalisation, the activation, the dropout of THE MASK above and, for the pooled calls, the token
+ * pooling of ampconv_pool_fwd / _bwd.  With T = N L tokens of D channels, x contiguous [T, D]:
+ *     mu_t = mean_c x[t, c];   var_t = mean_c (x[t, c] - mu_t)^2   (biased; from the centred values, not E[x^2] - mu^2)
+ *     rstd_t = 1 / sqrt(var_t + eps);   xhat = (x - mu) rstd;   z = xhat gamma[c] + beta[c]
+ * keep(i) and scale are those of THE MASK with i = t D + c, the flat index in the logical [N, L*D] tensor: a norm site
+ * with seed s drops the elements an act_dropout site with seed s drops.  act: AMPCONV_ACT_*.
+ *   norm_fwd:      y[t, c] = keep ? act(z) scale : 0;   stats[t] = (mu_t, rstd_t), fp32 [T, 2]
+ *   norm_bwd:      from x, dy, stats, gamma, beta (z is recomputed; act' from z: ReLU z > 0, ELU z > 0 ? 1 : exp(z)):
+ *                  dz = keep scale act'(z) dy;   dxhat = dz gamma;
+ *                  dx = rstd (dxhat - mean_c dxhat - xhat mean_c(dxhat xhat));
+ *                  dgamma[c] = sum_t dz xhat;   dbeta[c] = sum_t dz
+ *   norm_pool_fwd: x [N, L, D] -> pooled [N, D] = (1 / L) sum_l y[n, l, :] (AMPCONV_POOL_MEAN: one fp32 chain per output
+ *                  in ascending l), stats [N L, 2]; or y[n, 0, :] (AMPCONV_POOL_TOKEN0): only token 0 of a node is read
+ *                  and normalised, stats [N, 2]
+ *   norm_pool_bwd: norm_bwd with dy[n, l, :] = dpooled[n, :] / L (mean) or dpooled[n, :] for l = 0 (token 0: rows l > 0
+ *                  of dx are written as exact zeros and only token 0 contributes to dgamma, dbeta)
+ * SAVED for backward: x (the layer output, which the model keeps anyway) and stats, 8 bytes per token; nothing else of
+ * size [N, L*D].
+ * dtype: AMPCONV_F32 or AMPCONV_BF16 = the storage of x, y, dy, dx, pooled, dpooled; gamma, beta, stats, dgamma, dbeta
+ * and all arithmetic are fp32.  gamma and beta are both given or both NULL (= 1 and 0); dgamma and dbeta are both given
+ * or both NULL (not wanted: nothing is reduced, no workspace is needed) and must be NULL without gamma.  A token is
+ * owned by 4..64 lanes of one wave (the smallest power of two that covers the row's 16-byte pieces, at most 4 pieces per
+ * lane), read once, reduced by xor butterflies; bases that are not 16-byte aligned or a D that is no whole number of
+ * pieces (the XOR toy's D = 3) run element-wise.
+ * ERRORS: D outside 1..AMPCONV_NORM_MAX_D, L < 1, negative sizes, eps <= 0, an unknown act or pooling, threshold > 65535,
+ * a missing pointer: AMPCONV_E_BADARG; another dtype: AMPCONV_E_DTYPE; workspace_bytes below
+ * ampconv_norm_workspace_bytes(T, D) (T = N L for the pooled call) where dgamma is wanted: AMPCONV_E_WORKSPACE --
+ * nothing is launched.  T == 0 succeeds and writes dgamma = dbeta = 0.
+ * DETERMINISM.  Every output has the same bits on every launch.  dgamma, dbeta: no floating-point atomics -- each
+ * workgroup sums its tokens in a fixed order into its own [2, D] slot of `workspace` (need not be zeroed), a second
+ * kernel adds the slots in ascending order (16 consecutive runs of slots, then the 16 run sums); the grid depends on
+ * (T, D, dtype) only.  */
+#define AMPCONV_NORM_MAX_D 1024
+size_t ampconv_norm_workspace_bytes(int64_t T, int D);
+int ampconv_norm_fwd(const void *x, int64_t T, int D, const float *gamma, const float *beta, float eps, int act,
+                     uint64_t seed, uint32_t threshold, float scale, void *y, float *stats, int dtype, void *stream);
+int ampconv_norm_bwd(const void *x, const void *dy, const float *stats, int64_t T, int D, const float *gamma,
+                     const float *beta, int act, uint64_t seed, uint32_t threshold, float scale, void *dx,
+                     float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, int dtype, void *stream);
+int ampconv_norm_pool_fwd(const void *x, int64_t N, int L, int D, const float *gamma, const float *beta, float eps,
+                          int act, int pooling, uint64_t seed, uint32_t threshold, float scale, void *pooled,
+                          float *stats, int dtype, void *stream);
+int ampconv_norm_pool_bwd(const void *x, const void *dpooled, const float *stats, int64_t N, int L, int D,
+                          const float *gamma, const float *beta, int act, int pooling, uint64_t seed,
+                          uint32_t threshold, float scale, void *dx, float *dgamma, float *dbeta, void *workspace,
+                          size_t workspace_bytes, int dtype, void *stream);
 
 #ifdef __cplusplus
 }
