@@ -17,8 +17,9 @@ from .heatmap import AttentionHeatmap, top_features
 from .glue import ActDropout, TokenReadout, act_dropout, act_dropout_pool
 from .head import HeadMetrics, classifier_head, saint_nll_loss
 from .norm import NormTokenReadout, TokenLayerNorm, norm_act_dropout, norm_act_dropout_pool
+from .optim import FusedAdam
 
 __all__ = ['AMPConv', 'InvalidConfiguration', 'EdgeCSR', 'graph_cache', 'distributed', 'AMPGCN', 'FeatureTokens',
            'GraphSAINTRandomWalkSampler', 'NodePartition', 'PartitionedAMPConv', 'GraphedAMPConv', 'AttentionHeatmap', 'top_features',
            'ActDropout', 'TokenReadout', 'act_dropout', 'act_dropout_pool', 'HeadMetrics', 'classifier_head', 'saint_nll_loss',
-           'NormTokenReadout', 'TokenLayerNorm', 'norm_act_dropout', 'norm_act_dropout_pool']
+           'NormTokenReadout', 'TokenLayerNorm', 'norm_act_dropout', 'norm_act_dropout_pool', 'FusedAdam']

@@ -38,6 +38,16 @@ class WeightImage(ctypes.Structure):
     _fields_ = [('W', ctypes.c_void_p), ('stride_n', ctypes.c_int64), ('stride_k', ctypes.c_int64),
                 ('N', ctypes.c_int), ('K', ctypes.c_int), ('image', ctypes.c_void_p)]
 
+
+class AdamTensor(ctypes.Structure):
+    """ampconv_adam_tensor_t: one tensor of ampconv_adam_step / ampconv_adam_grad_norm (a HOST array of these)."""
+    _fields_ = [('p', ctypes.c_void_p), ('g', ctypes.c_void_p), ('m', ctypes.c_void_p), ('v', ctypes.c_void_p),
+                ('numel', ctypes.c_int64), ('step_size', ctypes.c_float), ('inv_bc2_sqrt', ctypes.c_float)]
+
+
+ADAM_MAX_TENSORS = 24     # AMPCONV_ADAM_MAX_TENSORS: descriptors per launch
+ADAM_CHUNK = 1024         # AMPCONV_ADAM_CHUNK: elements per workgroup
+
 # name -> (restype, argtypes); mirrors include/ampconv.h one to one
 SIGNATURES = {
     'ampconv_version': (_i32, []),
@@ -129,6 +139,10 @@ SIGNATURES = {
                                      ctypes.c_uint32, ctypes.c_float, _vp, _vp, _i32, _vp]),
     'ampconv_norm_pool_bwd': (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, ctypes.c_uint64, ctypes.c_uint32,
                                      ctypes.c_float, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
+    'ampconv_adam_workspace_bytes': (_sz, [ctypes.POINTER(AdamTensor), _i32]),
+    'ampconv_adam_grad_norm': (_i32, [ctypes.POINTER(AdamTensor), _i32, ctypes.c_float, _vp, _vp, _sz, _vp]),
+    'ampconv_adam_step': (_i32, [ctypes.POINTER(AdamTensor), _i32, ctypes.c_float, ctypes.c_double, ctypes.c_double,
+                                 ctypes.c_float, ctypes.c_float, _i32, ctypes.c_float, _vp, ctypes.c_float, _vp]),
 }
 
 _lib = None

@@ -27,6 +27,10 @@ class GradientAllReducer:
 
         reducer = GradientAllReducer(model.parameters())
         loss.backward(); reducer.allreduce(); optimizer.step()
+
+    With ampnet_amd.FusedAdam the unpack and the 1/world multiply ride on the optimizer's own pass:
+        loss.backward(); reducer.allreduce(unpack=False)
+        optimizer.step(grads=reducer.views, grad_scale=1 / world, set_to_none=True)
     """
 
     def __init__(self, params, group=None):
@@ -44,11 +48,22 @@ class GradientAllReducer:
                 off += p.numel()
         return self._flat
 
-    def allreduce(self, average=True):
+    @property
+    def views(self):
+        """Per-parameter views of the flat buffer, in the order of `params` (each of its parameter's shape): what
+        allreduce(unpack=False) leaves the reduced gradients in.  Needs the parameters' device, so at least one parameter."""
+        if self._flat is None:
+            self._buffer(self.params[0])
+        return list(self._views)
+
+    def allreduce(self, average=True, unpack=True):
         """average=True: mean over ranks (independent mini-batches per rank); False: sum (ranks hold
         partitions of ONE graph, ampnet_amd/partitioned.py).  Pack and unpack are ONE multi-tensor copy each
         (the payload is ~1 MB: on a 34 ms GraphSAINT step 2 x #parameters tiny launches would sit on the
-        critical path) and the 1/world factor rides on the unpack."""
+        critical path) and the 1/world factor rides on the unpack.
+        unpack=False: returns the SUMMED flat buffer -- no 1/world multiply whatever `average` says, nothing copied
+        back, every p.grad left as it was --; its per-parameter `views` and grad_scale = 1 / world go to
+        FusedAdam.step, which saves this pass one multi-tensor copy and one multiply."""
         if not self.params:
             return None
         world = dist.get_world_size(self.group)
@@ -59,6 +74,8 @@ class GradientAllReducer:
         if have:
             torch._foreach_copy_([self._views[i] for i in have], [self.params[i].grad for i in have])
         dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.group)      # also as the only rank: the same code path
+        if not unpack:
+            return flat
         if average and world > 1:
             flat.mul_(1.0 / world)
         for i, p in enumerate(self.params):

@@ -5,6 +5,7 @@ AMPGCN(D=128, H=4, L=20) + GraphSAINT random-walk batches + Adam + cosine warm r
 node_norm-weighted NLL.  Everything between the data and the loss runs on the GPU.
 
     python examples/train_graphsaint.py [--epochs 3] [--dropout 0.1 --fused-glue] [--fused-head] [--layer-norm]
+                                        [--fused-adam [--clip M] [--track-grad-norm]]
 """
 import argparse
 import os
@@ -17,7 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
-from ampnet_amd import AMPGCN, GraphSAINTRandomWalkSampler, HeadMetrics  # noqa: E402
+from ampnet_amd import AMPGCN, FusedAdam, GraphSAINTRandomWalkSampler, HeadMetrics  # noqa: E402
 
 
 def synthetic_cora(device, n=2708, f=1433, classes=7, seed=1):
@@ -57,7 +58,16 @@ def main():
     ap.add_argument('--fused-head', action='store_true',
                     help='Linear + log_softmax + node_norm-weighted NLL + train / test metrics as one HIP kernel per '
                          'direction (AMPGCN(fused_head=True).nll_loss): no read-back per step, one per epoch')
+    ap.add_argument('--fused-adam', action='store_true',
+                    help='ampnet_amd.FusedAdam instead of torch.optim.Adam: the whole step as one HIP launch, zero_grad() folded '
+                         'into it (step(set_to_none=True))')
+    ap.add_argument('--clip', type=float, default=None, metavar='M',
+                    help='with --fused-adam: clip the global gradient norm to M on the device (FusedAdam(max_grad_norm=M))')
+    ap.add_argument('--track-grad-norm', action='store_true',
+                    help="with --fused-adam: print the last batch's gradient norm with the epoch's read-back")
     args = ap.parse_args()
+    if (args.clip is not None or args.track_grad_norm) and not args.fused_adam:
+        ap.error('--clip and --track-grad-norm need --fused-adam')
     device = torch.device('cuda:0')
     torch.manual_seed(1)
     data = synthetic_cora(device)
@@ -68,7 +78,13 @@ def main():
                    layer_norm=args.layer_norm).to(device)
     loader = GraphSAINTRandomWalkSampler(data, batch_size=8, walk_length=150, num_steps=args.steps,
                                          sample_coverage=20, seed=1)
-    opt = torch.optim.Adam(model.parameters(), lr=0.005, weight_decay=1e-4)
+    if args.fused_adam:
+        opt = FusedAdam(model.parameters(), lr=0.005, weight_decay=1e-4, max_grad_norm=args.clip,
+                        track_grad_norm=args.track_grad_norm)
+        zero_grad, step = (lambda: None), (lambda: opt.step(set_to_none=True))
+    else:
+        opt = torch.optim.Adam(model.parameters(), lr=0.005, weight_decay=1e-4)
+        zero_grad, step = opt.zero_grad, opt.step
     sched = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(opt, T_0=400, T_mult=2)
     t0 = time.time()
     history = []
@@ -81,9 +97,9 @@ def main():
             metrics.zero_()
             for batch in loader:
                 model.train()
-                opt.zero_grad()
+                zero_grad()
                 model.nll_loss(batch, masks=(batch.train_mask, batch.test_mask), metrics=metrics).backward()
-                opt.step()
+                step()
                 sched.step()
                 cnt += 1
             m = metrics.read()                                              # the epoch's one read-back
@@ -94,14 +110,16 @@ def main():
             extra = ''
             for batch in loader:
                 model.train()
-                opt.zero_grad()
+                zero_grad()
                 out = model(batch)
                 loss = (F.nll_loss(out, batch.y, reduction='none') * batch.node_norm)[batch.train_mask].sum()
                 loss.backward()
-                opt.step()
+                step()
                 sched.step()
                 tot += loss.item(); cnt += 1
                 correct += float((out.argmax(1) == batch.y)[batch.train_mask].float().mean())
+        if args.fused_adam and opt.grad_norm is not None:
+            extra += f'  grad norm {float(opt.grad_norm):.4f}'                   # after the epoch's read-back: no extra wait
         history.append((tot / cnt, correct / cnt))
         torch.cuda.synchronize()
         print(f'epoch {epoch}: train loss {tot / cnt:.4f}  train acc {correct / cnt:.3f}{extra}  '

@@ -620,6 +620,53 @@ int ampconv_norm_pool_bwd(const void *x, const void *dpooled, const float *stats
                           uint32_t threshold, float scale, void *dx, float *dgamma, float *dbeta, void *workspace,
                           size_t workspace_bytes, int dtype, void *stream);
 
+/* ---- optimizer step (csrc/optim.hip; pure additions, the ABI number stays 111) ----------------------------------------
+ * Reference: every training script runs torch.optim.Adam with L2 weight decay (experiments/cora_benchmark_graphsaint.py:
+ * 84-85: lr=0.1, weight_decay=1e-4), most under CosineAnnealingWarmRestarts.  One launch updates a whole parameter group:
+ * `t` is a HOST array of n descriptors, one per tensor; all tensors are contiguous fp32 on the device.  At most
+ * AMPCONV_ADAM_MAX_TENSORS descriptors travel with one launch, BY VALUE as kernel arguments -- no device table, no
+ * host-to-device copy, no synchronisation --; n may be larger: a call issues ceil(n / AMPCONV_ADAM_MAX_TENSORS) launches.
+ *   adam_step: per element, all in fp32, with the tensor's step count t (bias corrections computed on the host in double):
+ *       c  = norm ? min(1, max_grad_norm / (*norm + 1e-6)) : 1        (torch.nn.utils.clip_grad_norm_; *norm is read ON
+ *                                                                       THE DEVICE)
+ *       g' = g * grad_scale * c
+ *       decoupled == 0:  g' += weight_decay * p                        (torch.optim.Adam)
+ *       decoupled == 1:  p  *= 1 - lr * weight_decay                   (torch.optim.AdamW)
+ *       m  = m + (1 - beta1) * (g' - m)
+ *       v  = beta2 * v + (1 - beta2) * g' * g'
+ *       p  = p - step_size * m / (sqrt(v) * inv_bc2_sqrt + eps)
+ *     p, m, v are updated in place; g is only read.  The betas are doubles: 1 - beta is formed in double and then
+ *     rounded to fp32 (in fp32, 1 - 0.999 is 1.3e-5 off 0.001, which would scale every g' * g').
+ *   adam_grad_norm: *norm = sqrt(sum over all n tensors of (g * grad_scale)^2), one fp32 value on the device.
+ * MAPPING.  Every tensor is cut into chunks of AMPCONV_ADAM_CHUNK elements, a workgroup per chunk (a chunk never
+ * straddles tensors); a tensor whose p, g, m and v are all 16-byte aligned is walked in 16-byte pieces with an
+ * element-wise tail, any other tensor element by element.  The grid depends on the numels only.
+ * DETERMINISM.  Every output has the same bits on every launch.  The norm: no floating-point atomics -- a lane's squares
+ * in ascending order, xor butterflies within a wave, the waves of a workgroup in wave order into the chunk's slot of
+ * `workspace` (ampconv_adam_workspace_bytes(t, n); need not be zeroed), and a second kernel adds the slots in ascending
+ * order (256 consecutive runs of slots, then the 256 run sums).  Alignment does not change the bits of the norm.
+ * ERRORS: n < 0, a NULL t with n > 0, a NULL p, g, m or v with numel > 0, a negative numel, more than 2^31 - 1 chunks,
+ * lr < 0, eps <= 0, a beta outside [0, 1), weight_decay < 0, max_grad_norm <= 0 with norm given, or a NULL norm in
+ * adam_grad_norm: AMPCONV_E_BADARG; workspace_bytes below ampconv_adam_workspace_bytes(t, n): AMPCONV_E_WORKSPACE --
+ * nothing is launched.  n == 0 and tensors with numel == 0 succeed; the norm of nothing is written as 0.  */
+#define AMPCONV_ADAM_MAX_TENSORS 24 /* descriptors per launch */
+#define AMPCONV_ADAM_CHUNK 1024     /* elements per workgroup */
+typedef struct {
+  float *p;           /* parameter */
+  const float *g;     /* gradient */
+  float *m;           /* exp_avg */
+  float *v;           /* exp_avg_sq */
+  int64_t numel;
+  float step_size;    /* lr / (1 - beta1^t) */
+  float inv_bc2_sqrt; /* 1 / sqrt(1 - beta2^t) */
+} ampconv_adam_tensor_t;
+size_t ampconv_adam_workspace_bytes(const ampconv_adam_tensor_t *t, int n);
+int ampconv_adam_grad_norm(const ampconv_adam_tensor_t *t, int n, float grad_scale, float *norm, void *workspace,
+                           size_t workspace_bytes, void *stream);
+int ampconv_adam_step(const ampconv_adam_tensor_t *t, int n, float lr, double beta1, double beta2, float eps,
+                      float weight_decay, int decoupled, float grad_scale, const float *norm, float max_grad_norm,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif
