@@ -28,9 +28,14 @@ def dev():
 
 SHAPES = [(500, 5000, 40, 100, 2), (400, 4000, 24, 128, 2), (300, 2500, 64, 128, 2), (400, 3000, 33, 72, 2),
           (300, 2500, 7, 100, 2), (300, 2500, 16, 68, 2), (400, 4000, 40, 128, 4), (300, 2500, 33, 40, 2),
-          (300, 2500, 24, 64, 4), (300, 2500, 12, 48, 2)]
+          (300, 2500, 24, 64, 4), (300, 2500, 12, 48, 2),
+          # the (vector width, waves NT, k-steps KS) instantiations of edge_block_x3.hip that nothing above and no random
+          # shape of this file or of test_gpu_parity.py reaches: dh % 4 != 0 -> two-element vectors, dh <= 32 -> KS = 1
+          (300, 2500, 7, 60, 2), (300, 2500, 24, 60, 2), (300, 2500, 40, 60, 2), (300, 2500, 50, 60, 2),
+          (300, 2500, 24, 68, 2), (300, 2500, 50, 100, 2), (300, 2500, 50, 48, 2), (300, 2500, 12, 80, 2)]
 IDS = ['class_default_L40_dh50', 'L24_dh64', 'L64_dh64', 'L33_dh36', 'L7_dh50', 'L16_dh34', 'L40_dh32', 'L33_dh20',
-       'L24_dh16', 'L12_dh24']
+       'L24_dh16', 'L12_dh24', 'L7_dh30_v2_nt1_ks1', 'L24_dh30_v2_nt2_ks1', 'L40_dh30_v2_nt3_ks1', 'L50_dh30_v2_nt4_ks1',
+       'L24_dh34_v2_nt2_ks2', 'L50_dh50_v2_nt4_ks2', 'L50_dh24_v4_nt4_ks1', 'L12_dh40_v4_nt1_ks2']
 
 
 @pytest.mark.parametrize('shape', SHAPES, ids=IDS)
@@ -49,6 +54,46 @@ def test_block_path_vs_fp64_oracle(shape, scaled, dev, monkeypatch):
     want = _oracle(layer, x, dy, ei, H)
     for name, a, b in zip(NAMES, got, want):
         assert_close_scaled(a, b, name)
+    assert (got[0][N - 20:] == 0).all(), 'rows with no in-edge must be exactly 0'
+
+
+# bf16 storage (one plane, csrc/edge_block_x3.hip's third format): test_gpu_parity.py::test_bf16_storage reaches the
+# workgroup-per-unit kernels at (4-element vectors, NT = 3, KS = 1) and (2, 3, 2) only; these are the other fourteen
+# (vector width, NT, KS).  Four-element vectors need dh % 4 == 0; L <= 20 with dh = 16 | 32 is another family's shape.
+BF16_SHAPES = [(300, 2500, 7, 60, 2), (300, 2500, 24, 60, 2), (300, 2500, 40, 60, 2), (300, 2500, 50, 60, 2),
+               (300, 2500, 12, 100, 2), (300, 2500, 24, 68, 2), (300, 2500, 50, 100, 2),
+               (300, 2500, 7, 48, 2), (300, 2500, 24, 48, 2), (300, 2500, 50, 48, 2),
+               (300, 2500, 12, 128, 2), (300, 2500, 24, 72, 2), (300, 2500, 33, 72, 2), (300, 2500, 64, 72, 2)]
+BF16_IDS = ['L7_dh30_v2_nt1_ks1', 'L24_dh30_v2_nt2_ks1', 'L40_dh30_v2_nt3_ks1', 'L50_dh30_v2_nt4_ks1',
+            'L12_dh50_v2_nt1_ks2', 'L24_dh34_v2_nt2_ks2', 'L50_dh50_v2_nt4_ks2',
+            'L7_dh24_v4_nt1_ks1', 'L24_dh24_v4_nt2_ks1', 'L50_dh24_v4_nt4_ks1',
+            'L12_dh64_v4_nt1_ks2', 'L24_dh36_v4_nt2_ks2', 'L33_dh36_v4_nt3_ks2', 'L64_dh36_v4_nt4_ks2']
+
+
+@pytest.mark.parametrize('shape', BF16_SHAPES, ids=BF16_IDS)
+def test_block_path_bf16_storage_vs_fp64_oracle(shape, dev, monkeypatch):
+    """The whole layer in bf16 storage (long segments in both directions: partial-tile stores and the combine pass's dK
+    convention; isolated nodes) against the fp64 oracle on the same bf16-rounded inputs and parameters, at the storage
+    mode's tolerance (rtol 2e-2, atol 2e-2 of the tensor's scale), as test_bf16_storage."""
+    from ampnet_amd import EdgeCSR
+    N, E, L, D, H = shape
+    layer, x, dy, ei = _make(N, E, L, D, H, dev)
+    layer = layer.to(torch.bfloat16)
+    x, dy = x.to(torch.bfloat16), dy.to(torch.bfloat16)
+    csr = EdgeCSR(ei.to(dev), N)
+    assert csr.hub_dst_chunks > 0 and csr.hub_src_chunks > 0
+    calls = _Calls(monkeypatch, SCALED_CALLS + F32_CALLS)
+    xg = x.to(dev).requires_grad_(True)
+    y = layer(xg, ei.to(dev))
+    assert y.dtype == torch.bfloat16
+    y.backward(dy.to(dev))
+    assert all(calls.n[k] == 1 for k in F32_CALLS) and all(calls.n[k] == 0 for k in SCALED_CALLS), calls.n
+    m = layer.multi_head_attention
+    got = [t.detach().float().cpu().numpy() for t in (y, xg.grad, m.in_proj_weight.grad, m.in_proj_bias.grad,
+                                                       m.out_proj.weight.grad, m.out_proj.bias.grad)]
+    want = _oracle(layer.float(), x.float(), dy.float(), ei, H)
+    for name, a, b in zip(NAMES, got, want):
+        assert_close_scaled(a, b, name, atol=2e-2, rtol=2e-2)
     assert (got[0][N - 20:] == 0).all(), 'rows with no in-edge must be exactly 0'
 
 
