@@ -13,6 +13,8 @@ EXPECTED_ABI = 111          # AMPCONV_VERSION of include/ampconv.h this binding 
 
 AMPCONV_F32 = 0
 AMPCONV_BF16 = 1
+PASS_FWD, PASS_DST, PASS_SRC = 0, 1, 2                                        # AMPCONV_PASS_*
+FAMILY_BF16_MFMA, FAMILY_SMALL, FAMILY_MFMA, FAMILY_BLOCK, FAMILY_GENERIC = range(5)     # AMPCONV_FAMILY_*
 HUB_CHUNK = int(os.environ.get('AMPCONV_HUB_CHUNK', 0))    # edges per chunk of a long CSR/CSC segment (include/ampconv.h, long segments); 0 = by size
 
 
@@ -66,6 +68,7 @@ SIGNATURES = {
                                     _vp, _vp, _vp, _i32, _vp]),
     'ampconv_bwd_edge_src': (_i32, [View, View, View, View, _vp, _vp, _vp, _i64, _i32, _i32, _i32,
                                     View, View, _vp, _i64, _vp, _vp, _vp, _i32, _vp]),
+    'ampconv_edge_family': (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, ctypes.POINTER(View), _i32]),
     'ampconv_attn_weights': (_i32, [View, View, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp]),
     'ampconv_attn_scores': (_i32, [View, View, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp]),
     'ampconv_attn_heatmap': (_i32, [View, View, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64,

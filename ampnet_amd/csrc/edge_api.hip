@@ -21,8 +21,14 @@ int check_common(int L, int D, int H, int dtype) {
   return AMPCONV_OK;
 }
 
-enum Pass { kFwd, kDst, kSrc };
-enum Family { kBf16, kSmall, kMfma, kBlock, kGeneric };
+enum Pass { kFwd = AMPCONV_PASS_FWD, kDst = AMPCONV_PASS_DST, kSrc = AMPCONV_PASS_SRC };
+enum Family {       // (the codes ampconv_edge_family reports)
+  kBf16 = AMPCONV_FAMILY_BF16_MFMA,
+  kSmall = AMPCONV_FAMILY_SMALL,
+  kMfma = AMPCONV_FAMILY_MFMA,
+  kBlock = AMPCONV_FAMILY_BLOCK,
+  kGeneric = AMPCONV_FAMILY_GENERIC
+};
 
 // The kernel family of one edge pass, or a negative AMPCONV_E_* code.  `stats`: the softmax statistics hand-off is in
 // use (written by the destination pass, read by the source pass) -- only the edge_mfma and workgroup-per-unit families
@@ -30,6 +36,12 @@ enum Family { kBf16, kSmall, kMfma, kBlock, kGeneric };
 // n = 0: the shape alone (ampconv_softmax_stats_bytes).
 int edge_family(Pass pass, int dtype, int L, int D, int H, bool stats, const ampconv_view_t *views, int n) {
   const bool bf = dtype == AMPCONV_BF16, fp = !bf && !force_generic();
+  if (stats && views) {
+    // a buffer can only have been sized by ampconv_softmax_stats_bytes, i.e. for the family of the shape alone: where
+    // that keeps none, `stats` must be NULL (a family that does keep them would write past whatever was passed)
+    const int sized_for = edge_family(kDst, dtype, L, D, H, false, nullptr, 0);
+    if (sized_for != kMfma && sized_for != kBlock) return sized_for < 0 ? sized_for : AMPCONV_E_BADARG;
+  }
   if (bf && ampconv_bf16_supported(L, D, H, views, n)) return stats ? AMPCONV_E_BADARG : kBf16;
   // bf16 storage of the other shapes: the workgroup-per-unit kernels widen / round the rows themselves (their source
   // pass exists only with the statistics)
@@ -105,13 +117,29 @@ extern "C" size_t ampconv_softmax_stats_bytes(int64_t E, int L, int D, int H, in
 extern "C" int ampconv_absmax(const void *X, int64_t ld, int64_t M, int K, int dtype, float *out, int reset, void *stream);
 
 namespace {
-// out_absmax of the backward passes for the kernel families that do not record it themselves: one pass over what was
-// just written, which must then be a row-major matrix (token rows of D contiguous channels, nodes L rows apart)
+// out_absmax of the backward passes for the kernel families that do not record it themselves: one ampconv_absmax pass
+// over what was just written, which must then be a row-major matrix that pass can walk in 16-byte pieces (token rows of
+// D contiguous channels, nodes L rows apart, base, D and row stride whole pieces).  The entry points ask BEFORE they
+// launch the pass: an error code means that nothing was written.
+bool absmax_view_ok(const ampconv_view_t &v, int L, int D, int H) {
+  return v.head_stride == D / H && v.node_stride == (int64_t)L * v.row_stride && v.row_stride >= D && D % 4 == 0 &&
+         v.row_stride % 4 == 0 && (uintptr_t)v.ptr % 16 == 0;
+}
 int view_absmax(const ampconv_view_t &v, int64_t n, int L, int D, int H, float *out, void *stream) {
-  if (v.head_stride != D / H || v.node_stride != (int64_t)L * v.row_stride) return AMPCONV_E_BADARG;
+  if (!absmax_view_ok(v, L, D, H)) return AMPCONV_E_BADARG;
   return ampconv_absmax(v.ptr, v.row_stride, n * L, D, AMPCONV_F32, out, 0, stream);
 }
 }  // namespace
+
+extern "C" int ampconv_edge_family(int pass, int dtype, int L, int D, int H, int stats, const ampconv_view_t *views,
+                                   int n) {
+  if (pass != AMPCONV_PASS_FWD && pass != AMPCONV_PASS_DST && pass != AMPCONV_PASS_SRC) return AMPCONV_E_BADARG;
+  if (int rc = check_common(L, D, H, dtype)) return rc;
+  if (n < 0 || (n > 0 && !views) || (stats && pass == AMPCONV_PASS_FWD)) return AMPCONV_E_BADARG;
+  for (int i = 0; i < n; ++i)
+    if (!view_ok(views[i])) return AMPCONV_E_BADARG;
+  return edge_family((Pass)pass, dtype, L, D, H, stats != 0, views, n);
+}
 
 extern "C" int ampconv_bwd_edge_dst(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V,
                                     ampconv_view_t dObar, const int32_t *rowptr,
@@ -130,6 +158,7 @@ extern "C" int ampconv_bwd_edge_dst(ampconv_view_t Q, ampconv_view_t K, ampconv_
   const int f = edge_family(kDst, dtype, L, D, H, stats, views, 5);
   if (f < 0) return f;
   const bool bf = dtype == AMPCONV_BF16, recorded = records_absmax(f, kDst);
+  if (out_absmax && !recorded && !absmax_view_ok(dQ, L, D, H)) return AMPCONV_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
   auto run = [&](int64_t n, HubArgs hub, const ampconv_view_t *o, float *absmax) {
     const StatsArgs sa{spos, stats, absmax};
@@ -165,6 +194,7 @@ extern "C" int ampconv_bwd_edge_src(ampconv_view_t Q, ampconv_view_t K, ampconv_
   const int f = edge_family(kSrc, dtype, L, D, H, stats, views, 6);
   if (f < 0) return f;
   const bool bf = dtype == AMPCONV_BF16, recorded = records_absmax(f, kSrc);
+  if (out_absmax && !recorded && !(absmax_view_ok(dK, L, D, H) && absmax_view_ok(dV, L, D, H))) return AMPCONV_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
   auto run = [&](int64_t n, HubArgs hub, const ampconv_view_t *o, float *absmax) {
     const StatsArgs sa{nullptr, const_cast<float *>(stats), absmax};

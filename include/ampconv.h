@@ -165,7 +165,9 @@ int ampconv_fwd_edge(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V,
  * gradient (SCALED MODE below); the caller zeroes it, both passes may share one.  The destination pass's tile kernels
  * record it as they store (one compare per wave); the source pass and the other kernel families get it from one
  * ampconv_absmax pass over the output, run by the entry point -- the output must then be a plain row-major matrix (rows
- * of D channels, a node's L rows consecutive).  */
+ * of D channels, a node's L rows consecutive: head_stride = dh, node_stride = L * row_stride >= L * D) that pass can walk
+ * in 16-byte pieces (base 16-byte aligned, D and row_stride multiples of 4).  Any other output view with out_absmax:
+ * AMPCONV_E_BADARG, checked BEFORE anything is launched -- nothing has been written.  */
 size_t ampconv_softmax_stats_bytes(int64_t E, int L, int D, int H, int dtype);
 int ampconv_bwd_edge_dst(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V,
                          ampconv_view_t dObar, const int32_t *rowptr,
@@ -180,6 +182,38 @@ int ampconv_bwd_edge_src(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V,
                          ampconv_view_t dV, const void *hub_plan, int64_t hub_chunks,
                          void *hub_ws, const float *stats, float *out_absmax, int dtype,
                          void *stream);
+
+/* ---- which kernels serve a call (a query: launches nothing, reads no device memory; a pure addition, the ABI number stays 111)
+ * The fp32 / bf16 entry points above choose a kernel family from dtype, shape, the statistics hand-off and the ALIGNMENT
+ * of every view of the call (base address and all three strides), in this order -- the first that applies:
+ *   AMPCONV_FAMILY_BF16_MFMA  bf16 storage, L <= 20, dh = 32 or 16, every view 16-byte aligned (base; strides multiples
+ *                             of 8).  Keeps no statistics: with `stats` AMPCONV_E_BADARG.
+ *   AMPCONV_FAMILY_SMALL      fp32, L <= 4, no statistics, a token row on at most 64 lanes of v = 1, 2 or 4 channels (the
+ *                             smallest v with D / v <= 64 and a head of dh / v = 4, 8, 16 or 32 lanes), every view
+ *                             aligned to v floats (base 4 v bytes; strides multiples of v).
+ *   AMPCONV_FAMILY_MFMA       fp32, L <= 20, dh = 32 or 16, every view 16-byte aligned (base; strides multiples of 4).
+ *   AMPCONV_FAMILY_BLOCK      fp32 or bf16, L <= 64, even dh <= 64, every view aligned to two elements (base 8 / 4 bytes;
+ *                             even strides); vectors of 4 elements where dh % 4 == 0 and every view allows it.  Its
+ *                             source pass exists only WITH the statistics; with statistics the fp32 shapes of
+ *                             AMPCONV_FAMILY_MFMA are not served (their buffer has that family's layout).
+ *   AMPCONV_FAMILY_GENERIC    fp32, any shape and any 4-byte aligned view; no statistics (AMPCONV_E_BADARG), no
+ *                             long-segment plan (it is ignored).
+ * bf16 storage that neither bf16 family serves: AMPCONV_E_DTYPE (so: no source pass at the bf16 MFMA shapes on views that
+ * are not 16-byte aligned).  A statistics buffer is taken only where ampconv_softmax_stats_bytes is non-zero for the
+ * shape, and only by the family that function sized it for: any other call with `stats` returns AMPCONV_E_BADARG (fp32,
+ * L <= 20, dh = 32 or 16 on 8-byte aligned views; every short-sequence shape) -- pass NULL there.  AMPCONV_FORCE_GENERIC=1 / AMPCONV_SMALL=0 in the
+ * environment act here as in the passes.  pass: AMPCONV_PASS_*; stats != 0: the call passes a statistics buffer
+ * (backward passes only); views: the n views of the call in argument order (Q, K, V[, dObar], outputs), n = 0: the shape
+ * alone.  Returns the family, or the negative AMPCONV_E_* the pass would return for these arguments.  */
+enum { AMPCONV_PASS_FWD = 0, AMPCONV_PASS_DST = 1, AMPCONV_PASS_SRC = 2 };
+enum {
+  AMPCONV_FAMILY_BF16_MFMA = 0,
+  AMPCONV_FAMILY_SMALL = 1,
+  AMPCONV_FAMILY_MFMA = 2,
+  AMPCONV_FAMILY_BLOCK = 3,
+  AMPCONV_FAMILY_GENERIC = 4
+};
+int ampconv_edge_family(int pass, int dtype, int L, int D, int H, int stats, const ampconv_view_t *views, int n);
 
 /* ---- edge phase on fp16 PLANES: fp32-grade results off the FP32 pipe (csrc/edge_mfma_f16x2.hip, ABI 106) --------
  * The same three passes (same reference arithmetic: torch functional.py:6578-6594 per edge, amp_conv.py:11, SURVEY.md

@@ -2,6 +2,8 @@
 
     python tools/bench_kernels.py [N E L D H] [--generic] [--bf16] [--hub] [--rmat] [--compact] [--absmax] [--planes] [--scaled]
 
+--layout=nhld|hnld|lnd|pad16|pad8|pad4|packed3: the inputs under that stride pattern of tests/edge_layouts.py (the same triples
+tests/test_gpu_edge_views.py checks against fp64); misaligned ones time the fall-back families.
 --planes: the plane-format passes of ABI 106 (csrc/edge_mfma_f16x2.hip) on the same random tensors, converted to two
 fp16 planes here (bounds 12 x the maxima, about what the a-priori bound of the projection gives).
 """
@@ -78,17 +80,24 @@ def main():
     print(f'csr build {timeit(lambda: EdgeCSR(ei, N, validate=False)):.3f} ms')
     Qv, Kv, Vv = (F_._view(qkv, i * D, L, dh) for i in range(3))
     dOv = F_._view(dobar, 0, L, dh)
-    # --layout=nhld / hnld: gathered inputs with contiguous per-(node, head) tiles (strided views, no kernel change)
+    # --layout=<id>: the inputs gathered into one of the stride patterns of tests/edge_layouts.py (layout_strides: nhld,
+    # hnld, lnd, pad16, pad8, pad4, ...) -- the layouts timed here are the ones tests/test_gpu_edge_views.py checks
     layout = next((a.split('=')[1] for a in sys.argv if a.startswith('--layout=')), 'nld')
     if layout != 'nld':
-        src4 = [qkv[:, i * D:(i + 1) * D].reshape(N, L, H, dh) for i in range(3)] + [dobar.reshape(N, L, H, dh)]
-        es = qkv.element_size()
-        if layout == 'nhld':
-            keep_in = [t.permute(0, 2, 1, 3).contiguous() for t in src4]          # [N, H, L, dh]
-            views = [_lib.View(t.data_ptr(), H * L * dh, dh, L * dh) for t in keep_in]
-        else:
-            keep_in = [t.permute(2, 0, 1, 3).contiguous() for t in src4]          # [H, N, L, dh]
-            views = [_lib.View(t.data_ptr(), L * dh, dh, N * L * dh) for t in keep_in]
+        sys.path.insert(0, os.path.join(ROOT, 'tests'))
+        from edge_layouts import layout_strides
+        ns, rs, hs, off = layout_strides(layout, N, L, H, dh, tdt == torch.bfloat16)
+        span = (N - 1) * ns + (L - 1) * rs + (H - 1) * hs + dh
+        n_, l_, h_, c_ = torch.meshgrid(torch.arange(N, device=dev) * ns, torch.arange(L, device=dev) * rs,
+                                        torch.arange(H, device=dev) * hs, torch.arange(dh, device=dev), indexing='ij')
+        index = (off + n_ + l_ + h_ + c_).reshape(-1)
+        src4 = [qkv[:, i * D:(i + 1) * D].reshape(N, L, H, dh) for i in range(3)] + [dobar[:, :D].reshape(N, L, H, dh)]
+        keep_in, views = [], []
+        for t in src4:
+            buf = torch.zeros(off + span, device=dev, dtype=tdt)
+            buf[index] = t.reshape(-1)
+            keep_in.append(buf)
+            views.append(_lib.View(buf.data_ptr() + off * buf.element_size(), ns, rs, hs))
         Qv, Kv, Vv, dOv = views
     print('input layout', layout)
     obar = torch.empty(N * L, D + pad, device=dev, dtype=tdt)
