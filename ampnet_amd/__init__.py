@@ -18,8 +18,10 @@ from .glue import ActDropout, TokenReadout, act_dropout, act_dropout_pool
 from .head import HeadMetrics, classifier_head, saint_nll_loss
 from .norm import NormTokenReadout, TokenLayerNorm, norm_act_dropout, norm_act_dropout_pool
 from .optim import FusedAdam
+from .stats import TensorStats, tensor_stats
 
 __all__ = ['AMPConv', 'InvalidConfiguration', 'EdgeCSR', 'graph_cache', 'distributed', 'AMPGCN', 'FeatureTokens',
            'GraphSAINTRandomWalkSampler', 'NodePartition', 'PartitionedAMPConv', 'GraphedAMPConv', 'AttentionHeatmap', 'top_features',
            'ActDropout', 'TokenReadout', 'act_dropout', 'act_dropout_pool', 'HeadMetrics', 'classifier_head', 'saint_nll_loss',
-           'NormTokenReadout', 'TokenLayerNorm', 'norm_act_dropout', 'norm_act_dropout_pool', 'FusedAdam']
+           'NormTokenReadout', 'TokenLayerNorm', 'norm_act_dropout', 'norm_act_dropout_pool', 'FusedAdam',
+           'TensorStats', 'tensor_stats']

@@ -50,6 +50,18 @@ class AdamTensor(ctypes.Structure):
 ADAM_MAX_TENSORS = 24     # AMPCONV_ADAM_MAX_TENSORS: descriptors per launch
 ADAM_CHUNK = 1024         # AMPCONV_ADAM_CHUNK: elements per workgroup
 
+
+class StatsTensor(ctypes.Structure):
+    """ampconv_stats_tensor_t: one tensor of the ampconv_stats_* calls (a HOST array of these)."""
+    _fields_ = [('x', ctypes.c_void_p), ('numel', ctypes.c_int64), ('dtype', ctypes.c_int)]
+
+
+STATS_MAX_TENSORS = 24    # AMPCONV_STATS_MAX_TENSORS: descriptors per launch
+STATS_CHUNK = 4096        # AMPCONV_STATS_CHUNK: elements one workgroup handles per iteration
+STATS_MAX_BINS = 2048     # AMPCONV_STATS_MAX_BINS
+STATS_MAX_RANKS = 4       # AMPCONV_STATS_MAX_RANKS: order statistics per call
+STATS_RECORD_BYTES = 88   # sizeof(ampconv_stats_record_t)
+
 # name -> (restype, argtypes); mirrors include/ampconv.h one to one
 SIGNATURES = {
     'ampconv_version': (_i32, []),
@@ -146,6 +158,11 @@ SIGNATURES = {
     'ampconv_adam_grad_norm': (_i32, [ctypes.POINTER(AdamTensor), _i32, ctypes.c_float, _vp, _vp, _sz, _vp]),
     'ampconv_adam_step': (_i32, [ctypes.POINTER(AdamTensor), _i32, ctypes.c_float, ctypes.c_double, ctypes.c_double,
                                  ctypes.c_float, ctypes.c_float, _i32, ctypes.c_float, _vp, ctypes.c_float, _vp]),
+    'ampconv_stats_workspace_bytes': (_sz, [ctypes.POINTER(StatsTensor), _i32]),
+    'ampconv_stats_moments': (_i32, [ctypes.POINTER(StatsTensor), _i32, _vp, _vp, _sz, _vp]),
+    'ampconv_stats_histogram': (_i32, [ctypes.POINTER(StatsTensor), _i32, _i32, _vp, _vp, _vp, _vp]),
+    'ampconv_stats_select': (_i32, [ctypes.POINTER(StatsTensor), _i32, ctypes.POINTER(ctypes.c_double), _i32, _vp, _vp,
+                                    _vp, _sz, _vp]),
 }
 
 _lib = None

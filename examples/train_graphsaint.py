@@ -5,7 +5,7 @@ AMPGCN(D=128, H=4, L=20) + GraphSAINT random-walk batches + Adam + cosine warm r
 node_norm-weighted NLL.  Everything between the data and the loss runs on the GPU.
 
     python examples/train_graphsaint.py [--epochs 3] [--dropout 0.1 --fused-glue] [--fused-head] [--layer-norm]
-                                        [--fused-adam [--clip M] [--track-grad-norm]]
+                                        [--fused-adam [--clip M] [--track-grad-norm]] [--diagnostics K [--diag-dir DIR]]
 """
 import argparse
 import os
@@ -41,6 +41,31 @@ def synthetic_cora(device, n=2708, f=1433, classes=7, seed=1):
                                  train_mask=mask(0, 1400).to(device), test_mask=mask(1400, n).to(device))
 
 
+def report(epoch, queued, model, diag_dir):
+    """The epoch's queued diagnostics: per layer, over the queued batches, mean |grad|, max |grad| and the non-finite
+    count; per activation site the dead share of a ReLU (zeros / numel); with diag_dir the reference's three figures for
+    the last queued batch."""
+    if not queued:
+        return
+    read = [(i, g.read(), a.read()) for i, g, a in queued]                  # behind the epoch's synchronise: no waiting
+    print(f'  diagnostics of epoch {epoch}, batches {[i for i, _, _ in read]}:')
+    for name in read[0][1]:
+        rows = [g[name] for _, g, _ in read]
+        print(f'    {name:48s} mean |grad| {sum(r["absmean"] for r in rows) / len(rows):.3e}  max |grad| '
+              f'{max(r["absmax"] for r in rows):.3e}  non-finite {sum(r["nan"] + r["inf"] for r in rows)}')
+    for name in read[0][2]:
+        rows = [a[name] for _, _, a in read]
+        dead = f'  dead {sum(r["zeros"] for r in rows) / max(sum(r["numel"] for r in rows), 1):.1%}' if 'ReLU' in name else ''
+        print(f'    {name:48s} mean {sum(r["mean"] for r in rows) / len(rows):+.3e}  std '
+              f'{sum(r["std"] for r in rows) / len(rows):.3e}{dead}  non-finite {sum(r["nan"] + r["inf"] for r in rows)}')
+    if diag_dir is not None:
+        i, g, a = read[-1]
+        os.makedirs(diag_dir, exist_ok=True)
+        model.plot_grad_flow(diag_dir, epoch, i, stats=g)
+        model.visualize_gradients(diag_dir, epoch, i, stats=g)
+        model.visualize_activations(diag_dir, None, epoch, i, stats=a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--epochs', type=int, default=3)
@@ -65,7 +90,15 @@ def main():
                     help='with --fused-adam: clip the global gradient norm to M on the device (FusedAdam(max_grad_norm=M))')
     ap.add_argument('--track-grad-norm', action='store_true',
                     help="with --fused-adam: print the last batch's gradient norm with the epoch's read-back")
+    ap.add_argument('--diagnostics', type=int, default=0, metavar='K',
+                    help="every K-th batch queues the reference's gradient and activation diagnostics (experiments/"
+                         'cora_benchmark_graphsaint.py:111-114) as device-side statistics (AMPGCN.gradient_stats / '
+                         "activation_stats); they are read and printed with the epoch's one read-back")
+    ap.add_argument('--diag-dir', default=None, metavar='DIR',
+                    help="with --diagnostics: write the reference's three figures for the last queued batch of every epoch there")
     args = ap.parse_args()
+    if args.diag_dir is not None and args.diagnostics <= 0:
+        ap.error('--diag-dir needs --diagnostics K')
     if (args.clip is not None or args.track_grad_norm) and not args.fused_adam:
         ap.error('--clip and --track-grad-norm need --fused-adam')
     device = torch.device('cuda:0')
@@ -89,8 +122,14 @@ def main():
     t0 = time.time()
     history = []
     metrics = HeadMetrics(2, device) if args.fused_head else None
+
+    def diagnose(queue, batch, i):                                          # after backward(), before the step
+        if args.diagnostics > 0 and i % args.diagnostics == 0:
+            queue.append((i, model.gradient_stats(), model.activation_stats(batch)))
+
     for epoch in range(args.epochs):
         tot = cnt = correct = 0
+        queued = []
         torch.cuda.synchronize()
         te = time.time()
         if args.fused_head:
@@ -99,6 +138,7 @@ def main():
                 model.train()
                 zero_grad()
                 model.nll_loss(batch, masks=(batch.train_mask, batch.test_mask), metrics=metrics).backward()
+                diagnose(queued, batch, cnt)
                 step()
                 sched.step()
                 cnt += 1
@@ -114,6 +154,7 @@ def main():
                 out = model(batch)
                 loss = (F.nll_loss(out, batch.y, reduction='none') * batch.node_norm)[batch.train_mask].sum()
                 loss.backward()
+                diagnose(queued, batch, cnt)
                 step()
                 sched.step()
                 tot += loss.item(); cnt += 1
@@ -122,6 +163,7 @@ def main():
             extra += f'  grad norm {float(opt.grad_norm):.4f}'                   # after the epoch's read-back: no extra wait
         history.append((tot / cnt, correct / cnt))
         torch.cuda.synchronize()
+        report(epoch, queued, model, args.diag_dir)
         print(f'epoch {epoch}: train loss {tot / cnt:.4f}  train acc {correct / cnt:.3f}{extra}  '
               f'({time.time() - t0:.1f} s; this epoch {time.time() - te:.3f} s = {1e3 * (time.time() - te) / cnt:.2f} ms '
               f'per sampled batch, sampler + 2 AMPConv layers fwd+bwd + Adam)', flush=True)

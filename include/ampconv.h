@@ -701,6 +701,86 @@ int ampconv_adam_step(const ampconv_adam_tensor_t *t, int n, float lr, double be
                       float weight_decay, int decoupled, float grad_scale, const float *norm, float max_grad_norm,
                       void *stream);
 
+/* ---- tensor statistics (csrc/stats.hip; pure additions, the ABI number stays 111) ----------------------------------------
+ * Reference: src/ampnet/module/amp_gcn.py:278-405 copies every weight gradient and five [N, L*D] activation tensors to the
+ * host and runs seaborn / numpy on them: 30- and 50-bin histograms, mean, median, std, abs().mean(), abs().max().  Here the
+ * same numbers come from a few streaming passes over the tensors where they lie; what a caller reads back is a record of
+ * 88 bytes, the bin counts and up to four order statistics per tensor.
+ * `t` is a HOST array of n descriptors, one per tensor: contiguous fp32 or bf16 (`dtype`: AMPCONV_F32 / AMPCONV_BF16) on the
+ * device.  At most AMPCONV_STATS_MAX_TENSORS descriptors travel with one launch, BY VALUE as kernel arguments; n may be
+ * larger: a call then repeats its launches per batch of descriptors.  Within a batch the number of launches does not depend
+ * on the number of tensors.  Every array argument below (records, range, counts, out) has one row per tensor, row i for
+ * t[i].  No call synchronises or copies to the host; `workspace` (ampconv_stats_workspace_bytes(t, n), the same buffer may
+ * serve the three calls one after the other on one stream) need not be zeroed.
+ * MAPPING.  A tensor is cut into chunks of AMPCONV_STATS_CHUNK elements; it gets min(chunks, 1024) workgroups of 256 lanes,
+ * workgroup w walks chunks w, w + workgroups, ...  A lane reads 16-byte pieces where the tensor's base is 16-byte aligned
+ * and the piece lies inside it, element by element otherwise -- the element-to-lane assignment is the same either way, so
+ * alignment changes no result bit.
+ * BITS, NOT COMPARISONS.  The library is compiled with -fno-honor-nans: `x != x`, isnan, fmin and fmax mean nothing on a
+ * NaN.  Every element is classified from its bit pattern (bf16 widened to fp32 by a shift) before any floating-point
+ * instruction sees it: exponent all ones and mantissa non-zero is a NaN, mantissa zero an infinity.  Only finite elements
+ * enter min / max / the sums / the histogram / the selection; min, max and the selection compare the order-preserving
+ * unsigned key of the bits (sign bit set: ~bits, else bits | 0x80000000; -0 is first rewritten to +0), absmax compares
+ * bits & 0x7fffffff.
+ *
+ *   stats_moments: one pass, records[i] = ampconv_stats_record_t of tensor i.  zero counts +0 and -0, negative counts
+ *     the finite x < 0 (not -0).  min, max, absmax are exact (a bf16 value widened to fp32); with finite == 0 they are NaN.
+ *     sum, sum_abs, sum_sq are over the finite elements, in fp64: a lane adds its elements in ascending order, the lanes of
+ *     a wave combine in an xor butterfly, the waves in wave order into the workgroup's slot of `workspace`, and a second
+ *     launch adds the slots of a tensor in ascending order (256 consecutive runs, then the run sums).  No floating-point
+ *     atomics: the same bits on every call.  mean = sum / finite, unbiased variance = (sum_sq - sum * sum / finite) /
+ *     (finite - 1) are left to the caller.
+ *   stats_histogram: ADDS to counts[i * (bins + 2) + b] (unsigned 64-bit; zero them for a fresh histogram) the number of
+ *     finite elements of tensor i in bin b of `bins` (1 .. AMPCONV_STATS_MAX_BINS) equal bins over [lo, hi]; index `bins`
+ *     counts the finite x < lo, index bins + 1 the finite x > hi.  (lo, hi) = range[2 i], range[2 i + 1] (device fp32) if
+ *     `range` is given, else records[i].min / .max READ ON THE DEVICE -- the pass may follow stats_moments on the stream
+ *     with no host round trip.  THE BIN RULE, in fp32 with these roundings and no others (a numpy model reproduces it):
+ *         scale = __fdiv_rn((float)bins, __fsub_rn(hi, lo));          hi == lo: every in-range element goes to bin 0
+ *         b     = min((int)floorf(__fmul_rn(__fsub_rn(x, lo), scale)), bins - 1)
+ *     A range with a NaN, an infinity, hi < lo, or so narrow that bins / (hi - lo) overflows is the caller's error: the
+ *     counts are then unspecified (never out of bounds).  Workgroups count in LDS (32-bit) and flush into the 64-bit global
+ *     counts with integer atomics, at the latest every 2^31 elements: integer addition commutes, the result does not
+ *     depend on the order of arrival.
+ *   stats_select: out[i * nq + j] (fp32) = the element of rank floor(q[j] * (finite - 1)) (in fp64, computed ON THE DEVICE
+ *     from records[i].finite) among the finite elements of tensor i in ascending order: numpy's quantile method 'lower';
+ *     q = 0.5 is rank (finite - 1) / 2, torch.median's lower median.  q: a HOST array of nq (1 .. AMPCONV_STATS_MAX_RANKS)
+ *     values in [0, 1].  Radix select on the key above: fp32 in three digit passes (11, 11, 10 bits), bf16 on the 16-bit
+ *     key in two (11, 5); a digit pass is the histogram kernel with another binning policy (bin = digit, for the elements
+ *     under the prefix chosen so far).  The result is an element of the tensor, bit for bit (-0 reads as +0); nothing is
+ *     interpolated.  finite == 0: NaN.
+ * These four entry points were added without a change of AMPCONV_VERSION (no existing argument list changed): a binding
+ * that declares them fails against an older 111 library at symbol lookup, not at the version check.
+ * NO MODE.  amp_gcn.py:297 also shows torch.mode: on continuous data every value is unique and it returns the minimum, on
+ * ReLU output it returns 0.  `zero` says the same thing honestly; there is no mode here.
+ * ERRORS: n < 0, a NULL t with n > 0, a NULL x with numel > 0, a negative numel, a NULL records / counts / out, bins or nq
+ * out of range, a q outside [0, 1]: AMPCONV_E_BADARG; a dtype other than the two: AMPCONV_E_DTYPE; workspace_bytes below the
+ * query: AMPCONV_E_WORKSPACE -- nothing is launched.  A failed launch or a failed memset of stats_select's tables comes
+ * back as the runtime's own POSITIVE hipError_t, as from every call of this header (conventions at the top; the Python
+ * binding's check() raises on any non-zero code).  n == 0 and tensors with numel == 0 succeed (all counts 0).  */
+#define AMPCONV_STATS_MAX_TENSORS 24 /* descriptors per launch */
+#define AMPCONV_STATS_CHUNK 4096     /* elements one workgroup handles per iteration */
+#define AMPCONV_STATS_MAX_BINS 2048
+#define AMPCONV_STATS_MAX_RANKS 4
+typedef struct {
+  const void *x;
+  int64_t numel;
+  int dtype; /* AMPCONV_F32 or AMPCONV_BF16 */
+} ampconv_stats_tensor_t;
+typedef struct {
+  int64_t numel, finite, nan, inf, zero, negative;
+  double sum, sum_abs, sum_sq; /* over the finite elements */
+  float min, max, absmax;      /* over the finite elements; NaN if there is none */
+  float reserved;
+} ampconv_stats_record_t; /* 88 bytes */
+size_t ampconv_stats_workspace_bytes(const ampconv_stats_tensor_t *t, int n);
+int ampconv_stats_moments(const ampconv_stats_tensor_t *t, int n, ampconv_stats_record_t *records, void *workspace,
+                          size_t workspace_bytes, void *stream);
+int ampconv_stats_histogram(const ampconv_stats_tensor_t *t, int n, int bins, const float *range,
+                            const ampconv_stats_record_t *records, uint64_t *counts, void *stream);
+int ampconv_stats_select(const ampconv_stats_tensor_t *t, int n, const double *q, int nq,
+                         const ampconv_stats_record_t *records, float *out, void *workspace, size_t workspace_bytes,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif
