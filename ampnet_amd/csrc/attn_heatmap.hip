@@ -293,10 +293,7 @@ __global__ __launch_bounds__(AMPCONV_WAVE) void heat_generic(HeatArgs a) {
   target_end<LDS>(a, tgt);
 }
 
-bool force_global() {
-  const char *e = std::getenv("AMPCONV_HEATMAP_GLOBAL");
-  return e && e[0] == '1';
-}
+bool force_global() { return env_switch("AMPCONV_HEATMAP_GLOBAL", false); }
 
 template <typename K>
 int set_dynamic_lds(K kernel, size_t bytes) {

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdlib>
 #include "../../include/ampconv.h"
 
 #define AMPCONV_WAVE 64
@@ -9,6 +10,24 @@
 static inline int ampconv_launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? AMPCONV_OK : (int)e;
+}
+
+// Launch of a wave-per-unit edge kernel (edge_mfma*.hip): a.n_units (row, head) units, `waves` of them per workgroup.
+template <typename Args>
+int launch_wave_units(void (*kernel)(Args), const Args &a, int waves, hipStream_t stream) {
+  const int64_t blocks = (a.n_units + waves - 1) / waves;
+  if (blocks > INT32_MAX) return AMPCONV_E_BADARG;
+  kernel<<<dim3((unsigned)blocks), dim3(64 * waves), 0, stream>>>(a);
+  return ampconv_launch_status();
+}
+
+// Boolean environment switch: "0..." switches a default-on switch off, "1..." a default-off switch on; anything else
+// is the default.  Reads the environment on every call: a switch that holds for the whole process keeps the result in
+// a function-local `static const bool`, one that tests flip inside a process (AMPCONV_FORCE_GENERIC, AMPCONV_SMALL) calls
+// this each time.
+static inline bool env_switch(const char *name, bool dflt) {
+  const char *e = std::getenv(name);
+  return (e && e[0] == (dflt ? '0' : '1')) ? !dflt : dflt;
 }
 
 // counter-based generator of the sampler, the featuriser and the dropout mask (include/ampconv.h, "THE MASK")

@@ -5,16 +5,10 @@
 #include "common.h"
 
 namespace {
-bool force_generic() {
-  const char *e = std::getenv("AMPCONV_FORCE_GENERIC");
-  return e && e[0] == '1';
-}
+bool force_generic() { return env_switch("AMPCONV_FORCE_GENERIC", false); }      // re-read on every call: tests flip it
 // short token sequences (L <= 4) have a family of their own (edge_small.hip); AMPCONV_SMALL=0 sends them to the tile
 // kernels instead (the tests cross-check the two)
-bool small_off() {
-  const char *e = std::getenv("AMPCONV_SMALL");
-  return e && e[0] == '0';
-}
+bool small_off() { return !env_switch("AMPCONV_SMALL", true); }      // re-read on every call, like AMPCONV_FORCE_GENERIC
 int check_common(int L, int D, int H, int dtype) {
   if (dtype != AMPCONV_F32 && dtype != AMPCONV_BF16) return AMPCONV_E_DTYPE;
   if (L <= 0 || D <= 0 || H <= 0 || D % H != 0) return AMPCONV_E_BADARG;

@@ -13,81 +13,40 @@
 //                                       in the same MFMA accumulators = PyG's mean numerator)
 // Reference arithmetic replaced: torch functional.py:6578 (scale), :6589 (QK^T), :6590
 // (softmax), :6594 (PV) per edge, and the mean aggregation of amp_conv.py:11.
-#include <cstdlib>
 #include "mfma_tile.h"
 
 namespace {
 
 constexpr float kLog2e = 1.4426950408889634f;
-#ifndef AMPCONV_WPB
-#define AMPCONV_WPB 4
-#endif
-constexpr int kWavesPerBlock = AMPCONV_WPB;
-// prefetch depth (edges in flight per wave) of the three kernels' register rings
-#ifndef AMPCONV_PF_FWD
-#define AMPCONV_PF_FWD 1
-#endif
-#ifndef AMPCONV_PF_DST
-#define AMPCONV_PF_DST 1
-#endif
-#ifndef AMPCONV_PF_SRC
-#define AMPCONV_PF_SRC 1
-#endif
+constexpr int kWavesPerBlock = 4;
+
+// What each batched-tail kernel is compiled for, per head width.  Every entry is a measured choice between builds that
+// both work; the kernels' code follows it (bwd_src_mfma_t4: where the statistics and the source's own operands live).
+template <int DH>
+struct Tune;
+template <>
+struct Tune<32> {
+  static constexpr int kFwdWaves = 4;      // waves per SIMD of the forward pass (128 registers; 3 = 168): 7.5 vs 8.1 ms
+  static constexpr int kDstWaves = 3;      // destination pass: 168 registers (2 = 256)
+  static constexpr int kSrcWaves = 3;      // source pass: 3 = 168 registers (own K / V operands re-read from LDS, statistics
+                                           // half an edge ahead), 2 = 256 (everything in registers, prefetch ring with
+                                           // the statistics): 115.8 vs 117.5 ms at cfg4
+  static constexpr int kSrcPrefetch = 1;   // edges in flight per wave in the source pass (2 and 4 need the 256 registers)
+};
+template <>
+struct Tune<16> {      // BASELINE config 3
+  static constexpr int kFwdWaves = 4;
+  static constexpr int kDstWaves = 4;      // one edge in flight
+  // source pass: 3 waves with a ring of two edges whose statistics travel with the tiles, against 4 waves with one
+  // edge in flight: 6.12 vs 6.37 ms at 100 k / 1 M, D=128, H=8
+  static constexpr int kSrcWaves = 3;
+  static constexpr int kSrcPrefetch = 2;
+};
 // addressing of the 4x4x1 phase-2 reads (mfma_tile.h, nt_accumulate): physical channel halves (fewer address registers,
 // 2-way LDS bank conflicts) or logical halves (conflict-free)
-#ifndef AMPCONV_NT_PHYS_FWD
-#define AMPCONV_NT_PHYS_FWD true     // keeps the forward pass at 128 registers = 4 waves per SIMD (1 spill instead of 7)
-#endif
-#ifndef AMPCONV_NT_PHYS_DST
-#define AMPCONV_NT_PHYS_DST false
-#endif
-#ifndef AMPCONV_NT_PHYS_SRC
-#define AMPCONV_NT_PHYS_SRC false
-#endif
-#ifndef AMPCONV_PF_DST_T4
-#define AMPCONV_PF_DST_T4 1      // main tiles in flight per wave in bwd_dst_mfma_t4 (1 or 2; 2 needs AMPCONV_DST_WAVES=2)
-#endif
-#ifndef AMPCONV_DST_WAVES
-#define AMPCONV_DST_WAVES 3      // waves per SIMD the destination pass is compiled for (168 registers; 2 = 256)
-#endif
-#ifndef AMPCONV_FWD_WAVES
-#define AMPCONV_FWD_WAVES 4      // waves per SIMD the forward pass is compiled for (128 registers; 3 = 168): 7.5 vs 8.1 ms
-#endif
-#ifndef AMPCONV_PF_FWD_T4
-#define AMPCONV_PF_FWD_T4 1      // main tiles in flight per wave in fwd_mfma_t4 (1 or 2; 2 needs AMPCONV_FWD_WAVES=3)
-#endif
-#ifndef AMPCONV_PF_SRC_T4
-#define AMPCONV_PF_SRC_T4 1      // edges in flight per wave in bwd_src_mfma_t4 (1, 2 or 4); 2 and 4 need AMPCONV_SRC_WAVES=2
-#endif
-// dh = 16 (BASELINE config 3): 4 waves per SIMD with one edge in flight, or 3 with a ring of AMPCONV_PF_SRC16 edges whose
-// statistics travel with the tiles
-#ifndef AMPCONV_DST16_WAVES
-#define AMPCONV_DST16_WAVES 4
-#endif
-#ifndef AMPCONV_PF_DST16
-#define AMPCONV_PF_DST16 1
-#endif
-#ifndef AMPCONV_SRC16_WAVES
-#define AMPCONV_SRC16_WAVES 3     // 6.12 vs 6.37 ms at 100 k / 1 M, D=128, H=8
-#endif
-#ifndef AMPCONV_PF_SRC16
-#define AMPCONV_PF_SRC16 2
-#endif
-#ifndef AMPCONV_SRC_WAVES
-#define AMPCONV_SRC_WAVES 3      // waves per SIMD the source pass is compiled for: 3 = 168 registers (own K / V operands
-                                 // re-read from LDS, statistics half an edge ahead), 2 = 256 (everything in registers,
-                                 // prefetch ring of AMPCONV_PF_SRC_T4 edges with their statistics): 115.8 vs 117.5 ms at cfg4
-#endif
-#ifdef AMPCONV_NO_SCHED_FENCE
-#define SCHED_FENCE()
-#else
-#define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#endif
-#ifdef AMPCONV_SETPRIO
-#define PRIO(x) __builtin_amdgcn_s_setprio(x)
-#else
-#define PRIO(x)
-#endif
+constexpr bool kNtPhysFwd = true;      // keeps the forward pass at 128 registers = 4 waves per SIMD (1 spill instead of 7)
+constexpr bool kNtPhysDst = false;
+constexpr bool kNtPhysSrc = false;
 
 struct FwdArgs {
   ampconv_view_t Q, K, V, O;
@@ -124,7 +83,7 @@ __device__ __forceinline__ float column_softmax(f32x4 &t0, f32x4 &t1, int L, int
   return m + __builtin_amdgcn_logf(l);
 }
 
-template <int DH, bool FULL, int PF>
+template <int DH, bool FULL>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void fwd_mfma(FwdArgs a) {
   using C = TileCfg<DH>;
   __shared__ __attribute__((aligned(16))) float lds_all[kWavesPerBlock][2][C::TILE_FLOATS];
@@ -156,25 +115,22 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void fwd_mfma(FwdArgs a) {
 #pragma unroll
   for (int mc = 0; mc < C::MC; ++mc) OT[mc][0] = OT[mc][1] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // register ring: the tiles of the next PF edges are in flight while one edge computes
-  PairRegs<DH> ring[PF];
+  // the tiles of the next edge are in flight (in registers) while one edge computes
+  PairRegs<DH> kv;
   IdxWindow win;
   if (beg < end) idxwin_load<false>(win, a.col, nullptr, beg, end, lane);
-  auto fetch = [&](PairRegs<DH> &buf, int p) {
+  auto fetch = [&](int p) {
     const int64_t s = idxwin_get<false>(win, a.col, nullptr, p, end, lane, nullptr);
-    pair_load<DH, FULL>(buf, tile_ptr<const float>(a.K, s, h), a.K.row_stride,
+    pair_load<DH, FULL>(kv, tile_ptr<const float>(a.K, s, h), a.K.row_stride,
                         tile_ptr<const float>(a.V, s, h), a.V.row_stride, L, lane);
   };
-#pragma unroll
-  for (int k = 0; k < PF; ++k)
-    if (beg + k < end) fetch(ring[k], beg + k);
-  auto step = [&](PairRegs<DH> &kv, int p) {
+  if (beg < end) fetch(beg);
+  for (int p = beg; p < end; ++p) {
     pair_to_lds<DH, FULL>(Kt, kv, 1.f, 1.f, L, lane);
-    if (p + PF < end) fetch(kv, p + PF);
+    if (p + 1 < end) fetch(p + 1);
     __builtin_amdgcn_wave_barrier();
 
     // S^T tiles [source-token tile mt][destination-token tile nt]
-    PRIO(1);
     f32x4 S[2][2];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
@@ -187,10 +143,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void fwd_mfma(FwdArgs a) {
         S[mt][1] = MFMA16(kA[kk], qB[1][kk], S[mt][1]);
       }
     }
-    PRIO(0);
     column_softmax<FULL>(S[0][0], S[1][0], L, g);
     column_softmax<FULL>(S[0][1], S[1][1], L, g);
-    PRIO(1);
 
     // O^T[channel tile mc][destination-token tile nt] += V^T P^T
 #pragma unroll
@@ -204,13 +158,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void fwd_mfma(FwdArgs a) {
         OT[mc][nt] = MFMA16(vA[4], S[1][nt][0], OT[mc][nt]);
       }
     }
-    PRIO(0);
     __builtin_amdgcn_wave_barrier();
-  };
-  for (int p0 = beg; p0 < end; p0 += PF) {
-#pragma unroll
-    for (int k = 0; k < PF; ++k)
-      if (p0 + k < end) step(ring[k], p0 + k);
   }
 
   // O^T C/D layout: lane (i' = lane & 15, g), reg q -> channel 4g + q + 16 mc, token i' + 16 nt
@@ -231,28 +179,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void fwd_mfma(FwdArgs a) {
   }
 }
 
-#ifdef AMPCONV_STAMPS
-// diagnostic build: per-phase s_memtime sums of bwd_src_mfma, written to a device buffer that
-// nothing else reads (tools/stamp_bwd_src.py); never part of the product build
-__device__ unsigned long long g_stamp_sums[8 * 4096];
-#define STAMP_DECL unsigned long long st_last, st_now, st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; \
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_last)::"memory");
-#define STAMP(i) do { __builtin_amdgcn_sched_barrier(0); \
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_now)::"memory"); \
-  __builtin_amdgcn_sched_barrier(0); st_acc[i] += st_now - st_last; st_last = st_now; } while (0)
-#define STAMP_FLUSH(unit) do { if ((unit) < 4096 && lane == 0) for (int i_ = 0; i_ < 8; ++i_) \
-  g_stamp_sums[(unit) * 8 + i_] = st_acc[i_]; } while (0)
-#else
-#define STAMP_DECL
-#define STAMP(i)
-#define STAMP_FLUSH(unit)
-#endif
-
-#ifdef AMPCONV_NO_ABSMAX      // A/B build without the out_absmax code (register pressure of the backward kernels)
-constexpr bool kRecordAbsmax = false;
-#else
-constexpr bool kRecordAbsmax = true;
-#endif
 struct BwdArgs;
 // BwdArgs::absmax, read from the kernel-argument segment where it is used (the kernel's epilogue) instead of being held
 // in scalar registers through the edge loop.  Only the DESTINATION pass records: the source pass sits exactly at its 168
@@ -286,15 +212,8 @@ __device__ __forceinline__ float *late_absmax_arg() {
 // ---- backward, destination pass: dQ[r], one wave per (destination, head).
 //   S^T = K Q^T, P^T = softmax;  dP^T = V dO^T;  delta = colsum(P^T o dP^T);
 //   dS^T = P^T o (dP^T - delta);  dQ^T += K^T dS^T   (dS^T C/D registers = B operand)
-#ifdef AMPCONV_OCC
-#define LB_DST __launch_bounds__(64 * kWavesPerBlock, 4)
-#define LB_SRC __launch_bounds__(64 * kWavesPerBlock, 3)
-#else
-#define LB_DST __launch_bounds__(64 * kWavesPerBlock)
-#define LB_SRC __launch_bounds__(64 * kWavesPerBlock)
-#endif
-template <int DH, bool FULL, int PF, bool STATS>
-__global__ LB_DST void bwd_dst_mfma(BwdArgs a) {
+template <int DH, bool FULL, bool STATS>
+__global__ __launch_bounds__(64 * kWavesPerBlock) void bwd_dst_mfma(BwdArgs a) {
   using C = TileCfg<DH>;
   __shared__ __attribute__((aligned(16))) float lds_all[kWavesPerBlock][2][C::TILE_FLOATS];
   const int lane = threadIdx.x & 63;
@@ -327,31 +246,28 @@ __global__ LB_DST void bwd_dst_mfma(BwdArgs a) {
 #pragma unroll
   for (int mc = 0; mc < C::MC; ++mc) dQT[mc][0] = dQT[mc][1] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  PairRegs<DH> ring[PF];
-  float ring_pos[PF];      // STATS: CSC position of the edge (int bits; rides in the window's weight slot)
+  PairRegs<DH> kv;         // the next edge's tiles, in flight while one edge computes
+  float pos;               // STATS: CSC position of that edge (int bits; rides in the window's weight slot)
   IdxWindow win;
   const float *wts = reinterpret_cast<const float *>(a.spos);
   if (beg < end) idxwin_load<STATS>(win, a.idx, wts, beg, end, lane);
-  auto fetch = [&](PairRegs<DH> &buf, float &pos, int p) {
+  auto fetch = [&](int p) {
     const int64_t s = idxwin_get<STATS>(win, a.idx, wts, p, end, lane, &pos);
-    pair_load<DH, FULL>(buf, tile_ptr<const float>(a.K, s, h), a.K.row_stride,
+    pair_load<DH, FULL>(kv, tile_ptr<const float>(a.K, s, h), a.K.row_stride,
                         tile_ptr<const float>(a.V, s, h), a.V.row_stride, L, lane);
   };
-#pragma unroll
-  for (int k = 0; k < PF; ++k)
-    if (beg + k < end) fetch(ring[k], ring_pos[k], beg + k);
-  auto step = [&](PairRegs<DH> &kv, float &pos, int p) {
+  if (beg < end) fetch(beg);
+  for (int p = beg; p < end; ++p) {
     pair_to_lds<DH, FULL>(Kt, kv, 1.f, 1.f, L, lane);
     float *sb = nullptr;
     if (STATS) sb = a.stats + ((int64_t)__builtin_bit_cast(int, pos) * a.H + h) * kStatsPerUnit;
-    if (p + PF < end) fetch(kv, pos, p + PF);
+    if (p + 1 < end) fetch(p + 1);
     __builtin_amdgcn_wave_barrier();
 
     // the destination-token columns of the two column tiles are independent (the softmax runs
     // along the source tokens = MFMA rows), so the tiles are processed one after the other
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-      PRIO(1);
       f32x4 S0, S1, dP0, dP1;                    // row tiles 0 / 1 of this column tile
       S0 = S1 = dP0 = dP1 = f32x4{0.f, 0.f, 0.f, 0.f};
       {
@@ -371,7 +287,6 @@ __global__ LB_DST void bwd_dst_mfma(BwdArgs a) {
           dP1 = MFMA16(vA[kk], dOB[nt][kk], dP1);
         }
       }
-      PRIO(0);
       const float lse = column_softmax<FULL>(S0, S1, L, g);
       float part = S1[0] * dP1[0];
 #pragma unroll
@@ -387,7 +302,6 @@ __global__ LB_DST void bwd_dst_mfma(BwdArgs a) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) S0[q] *= dP0[q] - delta;     // S now holds dS^T
       S1[0] *= dP1[0] - delta;
-      PRIO(1);
 #pragma unroll
       for (int mc = 0; mc < C::MC; ++mc) {
         float kC[5];
@@ -397,13 +311,7 @@ __global__ LB_DST void bwd_dst_mfma(BwdArgs a) {
         dQT[mc][nt] = MFMA16(kC[4], S1[0], dQT[mc][nt]);
       }
     }
-    PRIO(0);
     __builtin_amdgcn_wave_barrier();
-  };
-  for (int p0 = beg; p0 < end; p0 += PF) {
-#pragma unroll
-    for (int k = 0; k < PF; ++k)
-      if (p0 + k < end) step(ring[k], ring_pos[k], p0 + k);
   }
 
   float *ob = tile_ptr<float>(a.dQ, onode, h);
@@ -417,14 +325,12 @@ __global__ LB_DST void bwd_dst_mfma(BwdArgs a) {
         float4 o = make_float4(dQT[mc][nt][0] * oscale, dQT[mc][nt][1] * oscale,
                                dQT[mc][nt][2] * oscale, dQT[mc][nt][3] * oscale);
         *reinterpret_cast<float4 *>(ob + (int64_t)i * a.dQ.row_stride + 4 * g + 16 * mc) = o;
-        if (kRecordAbsmax) wmax = finite_abs_max(wmax, o);
+        wmax = finite_abs_max(wmax, o);
       }
     }
   }
-  if (kRecordAbsmax) {
-    float *const amax_p = late_absmax_arg();
-    if (amax_p) wave_record_absmax(amax_p, wmax);
-  }      // (partial-tile passes get no pointer: the combine pass records)
+  float *const amax_p = late_absmax_arg();
+  if (amax_p) wave_record_absmax(amax_p, wmax);      // (partial-tile passes get no pointer: the combine pass records)
 }
 
 // ---- backward, source pass: dK[s], dV[s], one wave per (source, head) over the CSC.
@@ -436,8 +342,8 @@ struct StatRegs {      // lse / delta of the destination tokens this lane's C/D 
   float l1, d1;        // token 16 + g
 };
 
-template <int DH, bool FULL, int PF, bool STATS>
-__global__ LB_SRC void bwd_src_mfma(BwdArgs a) {
+template <int DH, bool FULL, bool STATS>
+__global__ __launch_bounds__(64 * kWavesPerBlock) void bwd_src_mfma(BwdArgs a) {
   using C = TileCfg<DH>;
   __shared__ __attribute__((aligned(16))) float lds_all[kWavesPerBlock][2][C::TILE_FLOATS];
   const int lane = threadIdx.x & 63;
@@ -470,38 +376,31 @@ __global__ LB_SRC void bwd_src_mfma(BwdArgs a) {
   for (int mc = 0; mc < C::MC; ++mc)
     dKT[mc][0] = dKT[mc][1] = dVT[mc][0] = dVT[mc][1] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  STAMP_DECL
-  PairRegs<DH> ring[PF];
-  float ring_inv[PF];
-  StatRegs ring_st[PF];
+  PairRegs<DH> qg;         // the next edge's tiles, 1/in-degree and statistics, in flight while one edge computes
+  float inv;
+  StatRegs next_st;
   IdxWindow win;
   if (beg < end) idxwin_load<true>(win, a.idx, a.cinv, beg, end, lane);
-  auto fetch = [&](PairRegs<DH> &buf, float &inv, StatRegs &st, int p) {
+  auto fetch = [&](int p) {
     const int64_t d = idxwin_get<true>(win, a.idx, a.cinv, p, end, lane, &inv);
-    pair_load<DH, FULL>(buf, tile_ptr<const float>(a.Q, d, h), a.Q.row_stride,
+    pair_load<DH, FULL>(qg, tile_ptr<const float>(a.Q, d, h), a.Q.row_stride,
                         tile_ptr<const float>(a.dO, d, h), a.dO.row_stride, L, lane);
     if (STATS) {
       const float *sb = a.stats + ((int64_t)p * a.H + h) * kStatsPerUnit;
       const int g = lane >> 4;
-      st.l4 = *reinterpret_cast<const f32x4 *>(sb + 4 * g);
-      st.d4 = *reinterpret_cast<const f32x4 *>(sb + kLmax + 4 * g);
-      st.l1 = sb[16 + g];
-      st.d1 = sb[kLmax + 16 + g];
+      next_st.l4 = *reinterpret_cast<const f32x4 *>(sb + 4 * g);
+      next_st.d4 = *reinterpret_cast<const f32x4 *>(sb + kLmax + 4 * g);
+      next_st.l1 = sb[16 + g];
+      next_st.d1 = sb[kLmax + 16 + g];
     }
   };
-#pragma unroll
-  for (int k = 0; k < PF; ++k)
-    if (beg + k < end) fetch(ring[k], ring_inv[k], ring_st[k], beg + k);
-  auto step = [&](PairRegs<DH> &qg, float &inv, StatRegs &rs, int p) {
-    STAMP(0);
+  if (beg < end) fetch(beg);
+  for (int p = beg; p < end; ++p) {
     pair_to_lds<DH, FULL>(Qt, qg, a.qscale, inv, L, lane);
-    STAMP(1);
-    const StatRegs st = rs;
-    if (p + PF < end) fetch(qg, inv, rs, p + PF);
-    STAMP(2);
+    const StatRegs st = next_st;
+    if (p + 1 < end) fetch(p + 1);
     __builtin_amdgcn_wave_barrier();
 
-    PRIO(1);
     // the destination-token rows of the two row tiles are independent (the softmax runs along
     // the source tokens = lanes), so the tiles are processed one after the other: half the live
     // score registers
@@ -522,8 +421,6 @@ __global__ LB_SRC void bwd_src_mfma(BwdArgs a) {
           dP1 = MFMA16(gA[kk], vB[1][kk], dP1);
         }
       }
-      STAMP(3);
-      PRIO(0);
       // row softmax over the source tokens: columns n (+16 for tile 1) across the 16 lanes
 #pragma unroll
       for (int q = 0; q < (mt == 0 ? 4 : 1); ++q) {
@@ -548,8 +445,6 @@ __global__ LB_SRC void bwd_src_mfma(BwdArgs a) {
         dP0[q] = p0 * (dP0[q] - delta);       // dP now holds dS
         dP1[q] = p1 * (dP1[q] - delta);
       }
-      STAMP(4);
-      PRIO(1);
       const int ks = lane >> 4;
 #pragma unroll
       for (int t = (mt == 0 ? 0 : 4); t < (mt == 0 ? 4 : 5); ++t) {
@@ -565,17 +460,9 @@ __global__ LB_SRC void bwd_src_mfma(BwdArgs a) {
         }
       }
     }
-    STAMP(5);
-    PRIO(0);
     __builtin_amdgcn_wave_barrier();
-  };
-  for (int p0 = beg; p0 < end; p0 += PF) {
-#pragma unroll
-    for (int k = 0; k < PF; ++k)
-      if (p0 + k < end) step(ring[k], ring_inv[k], ring_st[k], p0 + k);
   }
 
-  STAMP_FLUSH(unit);
   const int g = lane >> 4;
   float *kb = tile_ptr<float>(a.dK, onode, h), *vb = tile_ptr<float>(a.dV, onode, h);
 #pragma unroll
@@ -652,15 +539,15 @@ __device__ __forceinline__ void pair_to_lds_tail(float *ldsA, float *stash, int 
 // phase-1 result (one register: lane (g, sg, j) = destination token 4 sg + g, source token 16 + j)
 // goes straight back in as the B operand of phase 2.
 template <int DH, bool FULL, bool NT4>
-__global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_SRC_WAVES : AMPCONV_SRC16_WAVES) void bwd_src_mfma_t4(BwdArgs a) {
+__global__ __launch_bounds__(64 * kWavesPerBlock, Tune<DH>::kSrcWaves) void bwd_src_mfma_t4(BwdArgs a) {
   using C = TileCfg<DH>;
   constexpr int kStash = 4 * 2 * 4 * DH;
   constexpr int NTM = NT4 ? 1 : 2;           // 16-wide column tiles on the 16x16x4 path
-  // FIXED_LDS (the 168-register build, AMPCONV_SRC_WAVES=3): the source's own K / V tiles live in LDS and their
-  // operands are re-read per phase (8 ds_read_b128) instead of holding 32 registers for the whole unit; the
-  // streamed images then keep only the 16 rows the main phase reads (tokens 16..19 go to the stash anyway):
-  // 13 312 B per wave = 3 blocks per CU
-  constexpr bool FIXED_LDS = NT4 && DH == 32 && AMPCONV_SRC_WAVES >= 3;
+  // FIXED_LDS (dh 32 on 4x4x1: what fits the kernel into the 168 registers of Tune<32>::kSrcWaves): the source's own
+  // K / V tiles live in LDS and their operands are re-read per phase (8 ds_read_b128) instead of holding 32 registers
+  // for the whole unit; the streamed images then keep only the 16 rows the main phase reads (tokens 16..19 go to the
+  // stash anyway): 13 312 B per wave = 3 blocks per CU.  dh 16 holds half as many operand registers and keeps them.
+  constexpr bool FIXED_LDS = NT4 && DH == 32;
   constexpr int kMain = FIXED_LDS ? 16 * DH : C::TILE_FLOATS;      // floats per streamed image
   constexpr int kFix = FIXED_LDS ? 2 * C::TILE_FLOATS : 0;
   __shared__ __attribute__((aligned(16))) float lds_all[kWavesPerBlock][2 * kMain + kStash + kFix];
@@ -671,7 +558,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_SRC_WAVES :
   int64_t s, onode;
   int h, beg, end, deg;
   if (!map_unit(a.hub, a.ptr, unit, a.n_units, a.H, s, onode, h, beg, end, deg)) return;
-  STAMP_DECL
   const int L = a.L, n = lane & 15, g = lane >> 4, sg = (lane >> 2) & 3, jt = lane & 3;
   float *Qt = lds_all[wave], *Gt = Qt + kMain, *stash = Qt + 2 * kMain;
   float *Kfix = stash + kStash, *Vfix = Kfix + C::TILE_FLOATS;
@@ -732,19 +618,18 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_SRC_WAVES :
     dK4[mc] = dV4[mc] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
-  // register ring: the tiles of the next PF edges are in flight while one edge computes (PF = 2 needs
-  // the 256-register budget of two waves per SIMD: AMPCONV_SRC_WAVES=2)
-  constexpr int PF = DH == 32 ? AMPCONV_PF_SRC_T4 : AMPCONV_PF_SRC16;
+  // register ring: the tiles of the next PF edges are in flight while one edge computes
+  constexpr int PF = Tune<DH>::kSrcPrefetch;
   PairRegs<DH> ring[PF];
   float ring_inv[PF];
   // statistics of an edge (lse / delta of its destination tokens 4g .. 4g+3 and, NT4, of token 4 sg + g).
-  // STATS_AHEAD: they travel with the edge's tiles, PF edges ahead; otherwise they are loaded at the start
-  // of the edge's own phase and the wave waits for them behind the first MFMAs (fewer live registers: what
-  // the 168-register build needs; the wait is hidden only while other waves keep the matrix pipe busy)
-  constexpr bool STATS_AHEAD = DH == 32 ? AMPCONV_SRC_WAVES < 3 : AMPCONV_SRC16_WAVES < 4;
-  // STATS_HALF (the 168-register build): no ring slot to spare, so the statistics of edge p + 1 are requested right
-  // after edge p's own have been consumed (end of phase 1) and arrive behind phase 2, ~60 % of an edge ahead of
-  // their use, in the registers the element-wise step has just freed
+  // STATS_AHEAD (dh 16, whose ring has the registers for it): they travel with the edge's tiles, PF edges ahead;
+  // otherwise (dh 32: 168 registers, no ring slot to spare) they are loaded at the start of the edge's own phase and
+  // the wave waits for them behind the first MFMAs (the wait is hidden only while other waves keep the matrix pipe busy)
+  constexpr bool STATS_AHEAD = DH == 16;
+  // STATS_HALF (dh 32 on 4x4x1): the statistics of edge p + 1 are requested right after edge p's own have been consumed
+  // (end of phase 1) and arrive behind phase 2, ~60 % of an edge ahead of their use, in the registers the element-wise
+  // step has just freed
   constexpr bool STATS_HALF = FIXED_LDS;
   struct EdgeStats { f32x4 l4, d4; float lT, dT; };
   EdgeStats ring_st[PF];
@@ -804,9 +689,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_SRC_WAVES :
       if (p >= end) break;
       PairRegs<DH> &qg = ring[e % PF];             // batches are 4 edges long: the ring slot of an edge is e % PF
       float &inv_next = ring_inv[e % PF];
-      STAMP(0);
       pair_to_lds_tail<DH, FULL, kMain>(Qt, stash, e, qg, a.qscale, inv_next, L, lane);
-      STAMP(1);
       EdgeStats st = ring_st[e % PF];
       if constexpr (STATS_HALF) st = next_st;
       else if constexpr (!STATS_AHEAD) load_stats(st, p);   // ahead of the tile loads of the next edge
@@ -814,7 +697,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_SRC_WAVES :
       const float lT = st.lT, dT = st.dT;
       if (p + PF < end) fetch(qg, inv_next, ring_st[e % PF], p + PF);
       __builtin_amdgcn_wave_barrier();
-      STAMP(2);
 
       // main tile: destination tokens 0..15 of this edge.  S first, then dP (NT4: one after the other
       // keeps only one row operand and one pair of result tiles live at a time)
@@ -835,8 +717,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_SRC_WAVES :
         pT = (vt && (FULL || 4 * sg + g < L)) ? fast_exp2(reduce_transpose(S1) - lT) : 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) S0[q] = v0 ? fast_exp2(S0[q] - l4[q]) : 0.f;
-        SCHED_FENCE();
-        STAMP(3);
+        __builtin_amdgcn_sched_barrier(0);
         {
           float gA[C::KK], b0[C::KK], bt[C::KK];
           rowop_from_lds<DH>(gA, Gt, 0, lane);
@@ -853,7 +734,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_SRC_WAVES :
         if constexpr (STATS_HALF) {
           load_stats(next_st, p + 1);
         }
-        STAMP(4);
       } else {
         {
           float qA[C::KK], gA[C::KK];
@@ -891,11 +771,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_SRC_WAVES :
         }
       }
       if constexpr (NT4) {
-        nt_accumulate<DH, AMPCONV_NT_PHYS_SRC>(dV4, Gt, nt_main, pT);
-        nt_accumulate<DH, AMPCONV_NT_PHYS_SRC>(dK4, Qt, nt_main, dsT);
+        nt_accumulate<DH, kNtPhysSrc>(dV4, Gt, nt_main, pT);
+        nt_accumulate<DH, kNtPhysSrc>(dK4, Qt, nt_main, dsT);
       }
       __builtin_amdgcn_wave_barrier();
-      STAMP(5);
     }
 
     // tail tile of the (up to) four edges p0 .. p0+3: lane group g <-> edge p0 + g
@@ -977,14 +856,12 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_SRC_WAVES :
         }
       }
       if constexpr (NT4) {      // tail-tile row 4 sg + x = (edge sg, token 16 + x): stash row 8 sg + 4 isG + x
-        nt_accumulate<DH, AMPCONV_NT_PHYS_SRC>(dV4, stash + 4 * DH, nt_stash, pT);
-        nt_accumulate<DH, AMPCONV_NT_PHYS_SRC>(dK4, stash, nt_stash, dsT);
+        nt_accumulate<DH, kNtPhysSrc>(dV4, stash + 4 * DH, nt_stash, pT);
+        nt_accumulate<DH, kNtPhysSrc>(dK4, stash, nt_stash, dsT);
       }
       __builtin_amdgcn_wave_barrier();
-      STAMP(6);
     }
   }
-  STAMP(7);
 
   float *kb = tile_ptr<float>(a.dK, onode, h), *vb = tile_ptr<float>(a.dV, onode, h);
 #pragma unroll
@@ -1002,8 +879,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_SRC_WAVES :
     }
   }
   if constexpr (NT4) {          // the four sg partial sums of every block column, then one quad stores
-    nt_fix_halves<DH, AMPCONV_NT_PHYS_SRC>(dK4, lane);
-    nt_fix_halves<DH, AMPCONV_NT_PHYS_SRC>(dV4, lane);
+    nt_fix_halves<DH, kNtPhysSrc>(dK4, lane);
+    nt_fix_halves<DH, kNtPhysSrc>(dV4, lane);
 #pragma unroll
     for (int hf = 0; hf < C::MC; ++hf) {
       float4 k4, v4;
@@ -1017,7 +894,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_SRC_WAVES :
       }
     }
   }
-  STAMP_FLUSH(unit);
 }
 
 // ---- forward with the tail tokens of four consecutive edges in one MFMA tile.
@@ -1108,7 +984,7 @@ __device__ __forceinline__ void tail_to_lds(float *img, const TailRegs<DH> &t, i
 // batch's tail tile (its row 4 sg + g = source token 16 + g of edge sg); phase 2 takes the probabilities
 // back as the B operand.  Per edge and head: 20 16x16x4 + 20 4x4x1 instead of 40 16x16x4.
 template <int DH, bool FULL, bool NT4>
-__global__ __launch_bounds__(64 * kWavesPerBlock, AMPCONV_FWD_WAVES) void fwd_mfma_t4(FwdArgs a) {
+__global__ __launch_bounds__(64 * kWavesPerBlock, Tune<DH>::kFwdWaves) void fwd_mfma_t4(FwdArgs a) {
   using C = TileCfg<DH>;
   constexpr int NTM = NT4 ? 1 : 2;           // 16-wide destination-token column tiles on the 16x16x4 path
   __shared__ __attribute__((aligned(16))) float lds_all[kWavesPerBlock][4 * 16 * DH];
@@ -1156,17 +1032,13 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, AMPCONV_FWD_WAVES) void fwd_mf
     o3 = idxwin_get<false>(win, a.col, nullptr, p_ + 3 < end ? p_ + 3 : end - 1, end, lane, nullptr); \
   } while (0)
   TailRegs<DH> ktn, vtn;
-  constexpr int PF = DH == 32 ? AMPCONV_PF_FWD_T4 : 1;     // main tiles of the next PF edges in flight (ring slot = e % PF)
-  MainRegs<DH> ring[PF];
+  MainRegs<DH> staged;         // main tiles of the next edge, in flight while one edge computes
   if (beg < end) {
     idxwin_load<false>(win, a.col, nullptr, beg, end, lane);
     AMPCONV_IDS(id0, id1, id2, id3, beg);
     tail_load<DH, FULL>(ktn, a.K, h, id0, id1, id2, id3, L, lane);
-    main_load<DH, FULL>(ring[0], tile_ptr<const float>(a.K, id0, h), a.K.row_stride,
+    main_load<DH, FULL>(staged, tile_ptr<const float>(a.K, id0, h), a.K.row_stride,
                         tile_ptr<const float>(a.V, id0, h), a.V.row_stride, L, lane);
-    if (PF == 2 && beg + 1 < end)
-      main_load<DH, FULL>(ring[PF - 1], tile_ptr<const float>(a.K, id1, h), a.K.row_stride,
-                          tile_ptr<const float>(a.V, id1, h), a.V.row_stride, L, lane);
   }
 
   for (int p0 = beg; p0 < end; p0 += 4) {
@@ -1219,13 +1091,12 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, AMPCONV_FWD_WAVES) void fwd_mf
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       if (p0 + e >= end) break;
-      main_to_lds<DH, FULL>(Kt, ring[e % PF], L, lane);
-      {      // edge p0 + e + PF: ids of this batch, then of the next (clamped ids are never fetched: has_next)
-        const bool has_next = p0 + e + PF < end;
-        const int next = PF == 1 ? (e == 0 ? id1 : e == 1 ? id2 : e == 2 ? id3 : nid0)
-                                 : (e == 0 ? id2 : e == 1 ? id3 : e == 2 ? nid0 : nid1);
+      main_to_lds<DH, FULL>(Kt, staged, L, lane);
+      {      // edge p0 + e + 1: ids of this batch, then of the next (clamped ids are never fetched: has_next)
+        const bool has_next = p0 + e + 1 < end;
+        const int next = e == 0 ? id1 : e == 1 ? id2 : e == 2 ? id3 : nid0;
         if (has_next)
-          main_load<DH, FULL>(ring[e % PF], tile_ptr<const float>(a.K, next, h), a.K.row_stride,
+          main_load<DH, FULL>(staged, tile_ptr<const float>(a.K, next, h), a.K.row_stride,
                               tile_ptr<const float>(a.V, next, h), a.V.row_stride, L, lane);
       }
       __builtin_amdgcn_wave_barrier();
@@ -1284,7 +1155,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, AMPCONV_FWD_WAVES) void fwd_mf
           for (int nt = 0; nt < NTM; ++nt) OT[mc][nt] = MFMA16(vA, S[nt][q], OT[mc][nt]);
         }
       }
-      if constexpr (NT4) nt_accumulate<DH, AMPCONV_NT_PHYS_FWD>(O4, Vt, nt_base, pz);
+      if constexpr (NT4) nt_accumulate<DH, kNtPhysFwd>(O4, Vt, nt_base, pz);
       __builtin_amdgcn_wave_barrier();
     }
 
@@ -1305,7 +1176,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, AMPCONV_FWD_WAVES) void fwd_mf
         for (int nt = 0; nt < NTM; ++nt) OT[mc][nt] = MFMA16(vA, St[nt][q], OT[mc][nt]);
       }
     }
-    if constexpr (NT4) nt_accumulate<DH, AMPCONV_NT_PHYS_FWD>(O4, Vtail, nt_base, PtT);   // row 4 sg + x = (edge sg, token 16 + x)
+    if constexpr (NT4) nt_accumulate<DH, kNtPhysFwd>(O4, Vtail, nt_base, PtT);   // row 4 sg + x = (edge sg, token 16 + x)
     __builtin_amdgcn_wave_barrier();
     id0 = nid0; id1 = nid1; id2 = nid2; id3 = nid3;
   }
@@ -1326,7 +1197,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, AMPCONV_FWD_WAVES) void fwd_mf
     }
   }
   if constexpr (NT4) {          // the four sg partial sums of every block column, then one quad stores
-    nt_fix_halves<DH, AMPCONV_NT_PHYS_FWD>(O4, lane);
+    nt_fix_halves<DH, kNtPhysFwd>(O4, lane);
 #pragma unroll
     for (int hf = 0; hf < C::MC; ++hf) {
       float4 o;
@@ -1379,7 +1250,7 @@ __device__ __forceinline__ void tail_dma(float *img, const ampconv_view_t &view,
 // 4 sg + g, destination token 16 + j); max, sum and delta of a column are all-reduces over the 16 lanes that
 // share j, quad sg == e folding in the batch's tail tile.  Per edge and head 30 16x16x4 + 30 4x4x1 instead of 60.
 template <int DH, bool FULL, bool STATS, bool NT4>
-__global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_DST_WAVES : AMPCONV_DST16_WAVES) void bwd_dst_mfma_t4(BwdArgs a) {
+__global__ __launch_bounds__(64 * kWavesPerBlock, Tune<DH>::kDstWaves) void bwd_dst_mfma_t4(BwdArgs a) {
   using C = TileCfg<DH>;
   constexpr int kImg = 16 * DH;
   // two separate LDS objects: the compiler orders every LDS read behind an LDS-DMA it cannot prove
@@ -1441,11 +1312,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_DST_WAVES :
     o2 = idxwin_get<STATS>(win, a.idx, wts, p_ + 2 < end ? p_ + 2 : end - 1, end, lane, &s2);           \
     o3 = idxwin_get<STATS>(win, a.idx, wts, p_ + 3 < end ? p_ + 3 : end - 1, end, lane, &s3);           \
   } while (0)
-  // main tiles of the next PF edges in flight (ring slot = e % PF).  The ordering argument for the LDS-DMA
-  // of the tail images below holds for PF = 2 as well: the DMA of batch b + 1 goes out in phase 0 of the FULL
-  // batch b ahead of that phase's staged loads, and phase 2 waits for exactly those loads.
-  constexpr int PF = DH == 32 ? AMPCONV_PF_DST_T4 : AMPCONV_PF_DST16;
-  MainRegs<DH> ring[PF];
+  MainRegs<DH> staged;         // main tiles of the next edge, in flight while one edge computes
   int cur = 0;
   if (beg < end) {
     idxwin_load<STATS>(win, a.idx, wts, beg, end, lane);
@@ -1453,11 +1320,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_DST_WAVES :
     __builtin_amdgcn_wave_barrier();
     tail_dma<DH, FULL>(tails, a.K, h, id0, id1, id2, id3, L, lane);
     tail_dma<DH, FULL>(tails + kImg, a.V, h, id0, id1, id2, id3, L, lane);
-    main_load<DH, FULL>(ring[0], tile_ptr<const float>(a.K, id0, h), a.K.row_stride,
+    main_load<DH, FULL>(staged, tile_ptr<const float>(a.K, id0, h), a.K.row_stride,
                         tile_ptr<const float>(a.V, id0, h), a.V.row_stride, L, lane);
-    if (PF == 2 && beg + 1 < end)
-      main_load<DH, FULL>(ring[PF - 1], tile_ptr<const float>(a.K, id1, h), a.K.row_stride,
-                          tile_ptr<const float>(a.V, id1, h), a.V.row_stride, L, lane);
   }
 
   for (int p0 = beg; p0 < end; p0 += 4) {
@@ -1517,18 +1381,17 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_DST_WAVES :
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       if (p0 + e >= end) break;
-      main_to_lds<DH, FULL>(Kt, ring[e % PF], L, lane);
+      main_to_lds<DH, FULL>(Kt, staged, L, lane);
       if (e == 0 && more) {          // next batch's tail rows -> the other pair of images; issued BEFORE
         float *Knext = tails + 2 * (cur ^ 1) * kImg;   // this phase's staged loads, so that the wait for
         tail_dma<DH, FULL>(Knext, a.K, h, nid0, nid1, nid2, nid3, L, lane);           // those (next phase)
         tail_dma<DH, FULL>(Knext + kImg, a.V, h, nid0, nid1, nid2, nid3, L, lane);    // does not stall on them
       }
       {
-        const bool has_next = p0 + e + PF < end;
-        const int next = PF == 1 ? (e == 0 ? id1 : e == 1 ? id2 : e == 2 ? id3 : nid0)
-                                 : (e == 0 ? id2 : e == 1 ? id3 : e == 2 ? nid0 : nid1);
+        const bool has_next = p0 + e + 1 < end;
+        const int next = e == 0 ? id1 : e == 1 ? id2 : e == 2 ? id3 : nid0;
         if (has_next)
-          main_load<DH, FULL>(ring[e % PF], tile_ptr<const float>(a.K, next, h), a.K.row_stride,
+          main_load<DH, FULL>(staged, tile_ptr<const float>(a.K, next, h), a.K.row_stride,
                               tile_ptr<const float>(a.V, next, h), a.V.row_stride, L, lane);
       }
       __builtin_amdgcn_wave_barrier();
@@ -1621,7 +1484,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_DST_WAVES :
           }
         }
         DsT = mineT ? pt * (dzt - delta) : DsT;                 // dS^T of edge e's tail rows
-        nt_accumulate<DH, AMPCONV_NT_PHYS_DST>(dQ4, Kt, nt_base, pz * (dz - delta));
+        nt_accumulate<DH, kNtPhysDst>(dQ4, Kt, nt_base, pz * (dz - delta));
       }
       __builtin_amdgcn_wave_barrier();
     }
@@ -1642,7 +1505,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_DST_WAVES :
         for (int nt = 0; nt < NTM; ++nt) dQT[mc][nt] = MFMA16(kC, dPt[nt][q], dQT[mc][nt]);
       }
     }
-    if constexpr (NT4) nt_accumulate<DH, AMPCONV_NT_PHYS_DST>(dQ4, Ktail, nt_base, DsT);   // row 4 sg + x = (edge sg, token 16 + x)
+    if constexpr (NT4) nt_accumulate<DH, kNtPhysDst>(dQ4, Ktail, nt_base, DsT);   // row 4 sg + x = (edge sg, token 16 + x)
     __builtin_amdgcn_wave_barrier();
     id0 = nid0; id1 = nid1; id2 = nid2; id3 = nid3;
     sp0 = nsp0; sp1 = nsp1; sp2 = nsp2; sp3 = nsp3;
@@ -1661,12 +1524,12 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_DST_WAVES :
         float4 o = make_float4(dQT[mc][nt][0] * oscale, dQT[mc][nt][1] * oscale,
                                dQT[mc][nt][2] * oscale, dQT[mc][nt][3] * oscale);
         *reinterpret_cast<float4 *>(ob + (int64_t)i * a.dQ.row_stride + 4 * g + 16 * mc) = o;
-        if (kRecordAbsmax) wmax = finite_abs_max(wmax, o);
+        wmax = finite_abs_max(wmax, o);
       }
     }
   }
   if constexpr (NT4) {          // the four sg partial sums of every block column, then one quad stores
-    nt_fix_halves<DH, AMPCONV_NT_PHYS_DST>(dQ4, lane);
+    nt_fix_halves<DH, kNtPhysDst>(dQ4, lane);
 #pragma unroll
     for (int hf = 0; hf < C::MC; ++hf) {
       float4 o;
@@ -1674,14 +1537,12 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, DH == 32 ? AMPCONV_DST_WAVES :
       o.z = quads_sum(dQ4[hf][2]) * oscale; o.w = quads_sum(dQ4[hf][3]) * oscale;
       if (sg == 0 && 16 + jt < L) {
         *reinterpret_cast<float4 *>(ob + (int64_t)(16 + jt) * a.dQ.row_stride + 16 * hf + 4 * g) = o;
-        if (kRecordAbsmax) wmax = finite_abs_max(wmax, o);
+        wmax = finite_abs_max(wmax, o);
       }
     }
   }
-  if (kRecordAbsmax) {
-    float *const amax_p = late_absmax_arg();
-    if (amax_p) wave_record_absmax(amax_p, wmax);
-  }
+  float *const amax_p = late_absmax_arg();
+  if (amax_p) wave_record_absmax(amax_p, wmax);
 }
 
 inline bool aligned16(const ampconv_view_t &v) {
@@ -1695,7 +1556,8 @@ inline bool aligned16(const ampconv_view_t &v) {
 // under the default scheduler, AMPCONV_PART=2 = the forward pass under `-mllvm -amdgpu-sched-strategy=iterative-minreg`
 // (the forward kernel sits exactly at the 128-register line of 4 waves per SIMD: the register-minimising scheduler
 // needs no spill there and runs 4-5 % faster, 76-79 vs 80-82 ms at cfg4; the two backward kernels lose 2-3 % under it).
-// AMPCONV_PART undefined: everything in one object.
+// A kernel is instantiated by the part whose entry point holds it in a kernel table: the forward tables, and so the forward
+// kernels, belong to part 2, the backward tables to part 1.  AMPCONV_PART undefined: everything in one object.
 #ifndef AMPCONV_PART
 #define AMPCONV_PART 0
 #endif
@@ -1714,87 +1576,70 @@ bool ampconv_mfma_views_ok(const ampconv_view_t *views, int n) {
 
 #endif  // AMPCONV_PART != 2
 
+// The kernel of a launch: tables indexed [dh == 16][L == kLmax] per pass and variant.  "Batched" = the `_t4` kernels
+// (AMPCONV_{FWD,DST,SRC}_T4=0: the plain ones), with the tail columns on 4x4x1 unless AMPCONV_{FWD,DST,SRC}_NT4=0;
+// both switches are read once per process.
 #if AMPCONV_PART != 1
 int ampconv_fwd_edge_mfma(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V,
                           const int32_t *rowptr, const int32_t *col, const int32_t *qidx,
                           int64_t n_rows, int L, int D, int H, ampconv_view_t O, HubArgs hub,
                           hipStream_t stream) {
+  typedef void (*Kernel)(FwdArgs);
+  static const Kernel plain[2][2] = {{fwd_mfma<32, false>, fwd_mfma<32, true>}, {fwd_mfma<16, false>, fwd_mfma<16, true>}};
+  static const Kernel batched[2][2][2] = {      // [nt4]
+      {{fwd_mfma_t4<32, false, false>, fwd_mfma_t4<32, true, false>}, {fwd_mfma_t4<16, false, false>, fwd_mfma_t4<16, true, false>}},
+      {{fwd_mfma_t4<32, false, true>, fwd_mfma_t4<32, true, true>}, {fwd_mfma_t4<16, false, true>, fwd_mfma_t4<16, true, true>}}};
+  static const bool t4 = env_switch("AMPCONV_FWD_T4", true), nt4 = env_switch("AMPCONV_FWD_NT4", true);
   const int dh = D / H;
-  FwdArgs a{Q, K, V, O, rowptr, col, qidx, hub, n_rows * H, L, H, kLog2e / sqrtf((float)dh)};
-  const int64_t blocks = (a.n_units + kWavesPerBlock - 1) / kWavesPerBlock;
-  if (blocks > INT32_MAX) return AMPCONV_E_BADARG;
-  const dim3 grid((unsigned)blocks), block(64 * kWavesPerBlock);
-  static const bool t4 = !(std::getenv("AMPCONV_FWD_T4") && std::getenv("AMPCONV_FWD_T4")[0] == '0');
-  static const bool nt4 = !(std::getenv("AMPCONV_FWD_NT4") && std::getenv("AMPCONV_FWD_NT4")[0] == '0');
-  if (t4 && L > 16) {                    // batched tails pay only if there are tail tokens
-    if (nt4) {                           // destination tail columns on 4x4x1
-      if (dh == 32 && L == kLmax) fwd_mfma_t4<32, true, true><<<grid, block, 0, stream>>>(a);
-      else if (dh == 32) fwd_mfma_t4<32, false, true><<<grid, block, 0, stream>>>(a);
-      else if (L == kLmax) fwd_mfma_t4<16, true, true><<<grid, block, 0, stream>>>(a);
-      else fwd_mfma_t4<16, false, true><<<grid, block, 0, stream>>>(a);
-    } else {
-      if (dh == 32 && L == kLmax) fwd_mfma_t4<32, true, false><<<grid, block, 0, stream>>>(a);
-      else if (dh == 32) fwd_mfma_t4<32, false, false><<<grid, block, 0, stream>>>(a);
-      else if (L == kLmax) fwd_mfma_t4<16, true, false><<<grid, block, 0, stream>>>(a);
-      else fwd_mfma_t4<16, false, false><<<grid, block, 0, stream>>>(a);
-    }
-    return ampconv_launch_status();
-  }
-  if (dh == 32 && L == kLmax) fwd_mfma<32, true, AMPCONV_PF_FWD><<<grid, block, 0, stream>>>(a);
-  else if (dh == 32) fwd_mfma<32, false, 1><<<grid, block, 0, stream>>>(a);
-  else if (L == kLmax) fwd_mfma<16, true, AMPCONV_PF_FWD><<<grid, block, 0, stream>>>(a);
-  else fwd_mfma<16, false, 1><<<grid, block, 0, stream>>>(a);
-  return ampconv_launch_status();
+  const FwdArgs a{Q, K, V, O, rowptr, col, qidx, hub, n_rows * H, L, H, kLog2e / sqrtf((float)dh)};
+  const auto &table = (t4 && L > 16) ? batched[nt4] : plain;      // batched tails pay only if there are tail tokens
+  return launch_wave_units(table[dh == 16][L == kLmax], a, kWavesPerBlock, stream);
 }
 
 #endif  // AMPCONV_PART != 1
 
 #if AMPCONV_PART != 2
+namespace {
+typedef void (*BwdKernel)(BwdArgs);
+// what the two backward passes share; the pass adds its outputs, its index arrays and oscale
+BwdArgs bwd_args(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, ampconv_view_t dO, const int32_t *ptr,
+                 const int32_t *idx, int64_t n, int L, int D, int H, HubArgs hub, StatsArgs st) {
+  BwdArgs a{};
+  a.hub = hub;
+  a.stats = st.stats; a.absmax = st.absmax;
+  a.Q = Q; a.K = K; a.V = V; a.dO = dO;
+  a.ptr = ptr; a.idx = idx;
+  a.n_units = n * H; a.L = L; a.H = H;
+  a.qscale = kLog2e / sqrtf((float)(D / H));
+  return a;
+}
+}  // namespace
+
 int ampconv_bwd_edge_dst_mfma(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V,
                               ampconv_view_t dO, const int32_t *rowptr, const int32_t *col,
                               int64_t n_rows, int L, int D, int H, ampconv_view_t dQ, HubArgs hub,
                               StatsArgs st, hipStream_t stream) {
+  static const BwdKernel plain[2][2][2] = {      // [stats]
+      {{bwd_dst_mfma<32, false, false>, bwd_dst_mfma<32, true, false>}, {bwd_dst_mfma<16, false, false>, bwd_dst_mfma<16, true, false>}},
+      {{bwd_dst_mfma<32, false, true>, bwd_dst_mfma<32, true, true>}, {bwd_dst_mfma<16, false, true>, bwd_dst_mfma<16, true, true>}}};
+  static const BwdKernel batched[2][2][2][2] = {      // [stats][nt4]
+      {{{bwd_dst_mfma_t4<32, false, false, false>, bwd_dst_mfma_t4<32, true, false, false>},
+        {bwd_dst_mfma_t4<16, false, false, false>, bwd_dst_mfma_t4<16, true, false, false>}},
+       {{bwd_dst_mfma_t4<32, false, false, true>, bwd_dst_mfma_t4<32, true, false, true>},
+        {bwd_dst_mfma_t4<16, false, false, true>, bwd_dst_mfma_t4<16, true, false, true>}}},
+      {{{bwd_dst_mfma_t4<32, false, true, false>, bwd_dst_mfma_t4<32, true, true, false>},
+        {bwd_dst_mfma_t4<16, false, true, false>, bwd_dst_mfma_t4<16, true, true, false>}},
+       {{bwd_dst_mfma_t4<32, false, true, true>, bwd_dst_mfma_t4<32, true, true, true>},
+        {bwd_dst_mfma_t4<16, false, true, true>, bwd_dst_mfma_t4<16, true, true, true>}}}};
+  static const bool t4 = env_switch("AMPCONV_DST_T4", true), nt4 = env_switch("AMPCONV_DST_NT4", true);
   const int dh = D / H;
-  BwdArgs a{};
-  a.hub = hub;
-  a.spos = st.spos; a.stats = st.stats; a.absmax = st.absmax;
-  a.Q = Q; a.K = K; a.V = V; a.dO = dO; a.dQ = dQ;
-  a.ptr = rowptr; a.idx = col; a.cinv = nullptr;
-  a.n_units = n_rows * H; a.L = L; a.H = H;
-  a.qscale = kLog2e / sqrtf((float)dh);
+  BwdArgs a = bwd_args(Q, K, V, dO, rowptr, col, n_rows, L, D, H, hub, st);
+  a.spos = st.spos;
+  a.dQ = dQ;
   a.oscale = 1.f / sqrtf((float)dh);
-  const int64_t blocks = (a.n_units + kWavesPerBlock - 1) / kWavesPerBlock;
-  if (blocks > INT32_MAX) return AMPCONV_E_BADARG;
-  const dim3 grid((unsigned)blocks), block(64 * kWavesPerBlock);
-  static const bool t4 = !(std::getenv("AMPCONV_DST_T4") && std::getenv("AMPCONV_DST_T4")[0] == '0');
-  static const bool nt4 = !(std::getenv("AMPCONV_DST_NT4") && std::getenv("AMPCONV_DST_NT4")[0] == '0');
-  if (t4 && L > 16) {                    // batched tails pay only if there are tail tokens
-#define AMPCONV_DST_LAUNCH(DH_, FULL_)                                                                  \
-  do {                                                                                                  \
-    if (st.stats && nt4) bwd_dst_mfma_t4<DH_, FULL_, true, true><<<grid, block, 0, stream>>>(a);        \
-    else if (st.stats) bwd_dst_mfma_t4<DH_, FULL_, true, false><<<grid, block, 0, stream>>>(a);         \
-    else if (nt4) bwd_dst_mfma_t4<DH_, FULL_, false, true><<<grid, block, 0, stream>>>(a);              \
-    else bwd_dst_mfma_t4<DH_, FULL_, false, false><<<grid, block, 0, stream>>>(a);                      \
-  } while (0)
-    if (dh == 32 && L == kLmax) AMPCONV_DST_LAUNCH(32, true);
-    else if (dh == 32) AMPCONV_DST_LAUNCH(32, false);
-    else if (L == kLmax) AMPCONV_DST_LAUNCH(16, true);
-    else AMPCONV_DST_LAUNCH(16, false);
-#undef AMPCONV_DST_LAUNCH
-    return ampconv_launch_status();
-  }
-  if (st.stats) {
-    if (dh == 32 && L == kLmax) bwd_dst_mfma<32, true, AMPCONV_PF_DST, true><<<grid, block, 0, stream>>>(a);
-    else if (dh == 32) bwd_dst_mfma<32, false, 1, true><<<grid, block, 0, stream>>>(a);
-    else if (L == kLmax) bwd_dst_mfma<16, true, AMPCONV_PF_DST, true><<<grid, block, 0, stream>>>(a);
-    else bwd_dst_mfma<16, false, 1, true><<<grid, block, 0, stream>>>(a);
-  } else {
-    if (dh == 32 && L == kLmax) bwd_dst_mfma<32, true, AMPCONV_PF_DST, false><<<grid, block, 0, stream>>>(a);
-    else if (dh == 32) bwd_dst_mfma<32, false, 1, false><<<grid, block, 0, stream>>>(a);
-    else if (L == kLmax) bwd_dst_mfma<16, true, AMPCONV_PF_DST, false><<<grid, block, 0, stream>>>(a);
-    else bwd_dst_mfma<16, false, 1, false><<<grid, block, 0, stream>>>(a);
-  }
-  return ampconv_launch_status();
+  const bool stats = st.stats != nullptr;
+  const auto &table = (t4 && L > 16) ? batched[stats][nt4] : plain[stats];      // batched tails pay only if there are tail tokens
+  return launch_wave_units(table[dh == 16][L == kLmax], a, kWavesPerBlock, stream);
 }
 
 int ampconv_bwd_edge_src_mfma(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V,
@@ -1802,50 +1647,22 @@ int ampconv_bwd_edge_src_mfma(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t
                               const float *cinv, int64_t n_src, int L, int D, int H,
                               ampconv_view_t dK, ampconv_view_t dV, HubArgs hub, StatsArgs st,
                               hipStream_t stream) {
-  const int dh = D / H;
-  BwdArgs a{};
-  a.hub = hub;
-  a.stats = st.stats; a.absmax = st.absmax;
-  a.Q = Q; a.K = K; a.V = V; a.dO = dO; a.dK = dK; a.dV = dV;
-  a.ptr = cscptr; a.idx = crow; a.cinv = cinv;
-  a.n_units = n_src * H; a.L = L; a.H = H;
-  a.qscale = kLog2e / sqrtf((float)dh);
+  static const BwdKernel plain[2][2][2] = {      // [stats]
+      {{bwd_src_mfma<32, false, false>, bwd_src_mfma<32, true, false>}, {bwd_src_mfma<16, false, false>, bwd_src_mfma<16, true, false>}},
+      {{bwd_src_mfma<32, false, true>, bwd_src_mfma<32, true, true>}, {bwd_src_mfma<16, false, true>, bwd_src_mfma<16, true, true>}}};
+  static const BwdKernel batched[2][2][2] = {      // [nt4]; these exist only with the statistics of the destination pass
+      {{bwd_src_mfma_t4<32, false, false>, bwd_src_mfma_t4<32, true, false>}, {bwd_src_mfma_t4<16, false, false>, bwd_src_mfma_t4<16, true, false>}},
+      {{bwd_src_mfma_t4<32, false, true>, bwd_src_mfma_t4<32, true, true>}, {bwd_src_mfma_t4<16, false, true>, bwd_src_mfma_t4<16, true, true>}}};
+  static const bool t4 = env_switch("AMPCONV_SRC_T4", true), nt4 = env_switch("AMPCONV_SRC_NT4", true);
+  BwdArgs a = bwd_args(Q, K, V, dO, cscptr, crow, n_src, L, D, H, hub, st);
+  a.cinv = cinv;
+  a.dK = dK; a.dV = dV;
   a.oscale = 0.6931471805599453f;     // dK = ln2 * sum dS^T (Q * log2e / sqrt(dh))
-  const int64_t blocks = (a.n_units + kWavesPerBlock - 1) / kWavesPerBlock;
-  if (blocks > INT32_MAX) return AMPCONV_E_BADARG;
-  const dim3 grid((unsigned)blocks), block(64 * kWavesPerBlock);
-  static const bool t4 = !(std::getenv("AMPCONV_SRC_T4") && std::getenv("AMPCONV_SRC_T4")[0] == '0');
-  static const bool nt4 = !(std::getenv("AMPCONV_SRC_NT4") && std::getenv("AMPCONV_SRC_NT4")[0] == '0');
-  // developer knob: unused dynamic LDS per block, to lower the occupancy in experiments
-  static const unsigned dyn = std::getenv("AMPCONV_SRC_DYNLDS") ? (unsigned)atoi(std::getenv("AMPCONV_SRC_DYNLDS")) : 0u;
-  if (st.stats && t4 && nt4 && L > 16) {       // tail columns on 4x4x1 (only if there are tail tokens)
-    if (dh == 32 && L == kLmax) bwd_src_mfma_t4<32, true, true><<<grid, block, dyn, stream>>>(a);
-    else if (dh == 32) bwd_src_mfma_t4<32, false, true><<<grid, block, dyn, stream>>>(a);
-    else if (L == kLmax) bwd_src_mfma_t4<16, true, true><<<grid, block, dyn, stream>>>(a);
-    else bwd_src_mfma_t4<16, false, true><<<grid, block, dyn, stream>>>(a);
-  } else if (st.stats && t4) {
-    if (dh == 32 && L == kLmax) bwd_src_mfma_t4<32, true, false><<<grid, block, dyn, stream>>>(a);
-    else if (dh == 32) bwd_src_mfma_t4<32, false, false><<<grid, block, dyn, stream>>>(a);
-    else if (L == kLmax) bwd_src_mfma_t4<16, true, false><<<grid, block, dyn, stream>>>(a);
-    else bwd_src_mfma_t4<16, false, false><<<grid, block, dyn, stream>>>(a);
-  } else if (st.stats) {
-    if (dh == 32 && L == kLmax) bwd_src_mfma<32, true, AMPCONV_PF_SRC, true><<<grid, block, dyn, stream>>>(a);
-    else if (dh == 32) bwd_src_mfma<32, false, 1, true><<<grid, block, dyn, stream>>>(a);
-    else if (L == kLmax) bwd_src_mfma<16, true, AMPCONV_PF_SRC, true><<<grid, block, dyn, stream>>>(a);
-    else bwd_src_mfma<16, false, 1, true><<<grid, block, dyn, stream>>>(a);
-  } else {
-    if (dh == 32 && L == kLmax) bwd_src_mfma<32, true, AMPCONV_PF_SRC, false><<<grid, block, dyn, stream>>>(a);
-    else if (dh == 32) bwd_src_mfma<32, false, 1, false><<<grid, block, dyn, stream>>>(a);
-    else if (L == kLmax) bwd_src_mfma<16, true, AMPCONV_PF_SRC, false><<<grid, block, dyn, stream>>>(a);
-    else bwd_src_mfma<16, false, 1, false><<<grid, block, dyn, stream>>>(a);
-  }
-  return ampconv_launch_status();
+  const bool stats = st.stats != nullptr;
+  // with the statistics the batched kernel runs at every L (its element-wise softmax is what the statistics buy);
+  // tail columns on 4x4x1 only if there are tail tokens
+  const auto &table = (stats && t4) ? batched[nt4 && L > 16] : plain[stats];
+  return launch_wave_units(table[D / H == 16][L == kLmax], a, kWavesPerBlock, stream);
 }
 
 #endif  // AMPCONV_PART != 2
-
-#if defined(AMPCONV_STAMPS) && AMPCONV_PART != 2
-extern "C" int ampconv_debug_read_stamps(unsigned long long *host_out, int n) {
-  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamp_sums), sizeof(unsigned long long) * n);
-}
-#endif

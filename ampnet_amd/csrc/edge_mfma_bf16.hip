@@ -662,11 +662,7 @@ int launch(Args &a, int L, int D, int H, EdgeKernel const (&kernels)[4], hipStre
   if (dh != DH && dh != DH / 2) return AMPCONV_E_BADARG;
   a.qscale = kLog2e / sqrtf((float)dh);
   a.oscale = 1.f / sqrtf((float)dh);
-  const int64_t blocks = (a.n_units + kWavesPerBlock - 1) / kWavesPerBlock;
-  if (blocks > INT32_MAX) return AMPCONV_E_BADARG;
-  const dim3 grid((unsigned)blocks), block(64 * kWavesPerBlock);
-  kernels[2 * (dh == DH / 2) + (L == kLmax)]<<<grid, block, 0, stream>>>(a);
-  return ampconv_launch_status();
+  return launch_wave_units(kernels[2 * (dh == DH / 2) + (L == kLmax)], a, kWavesPerBlock, stream);
 }
 
 inline bool aligned16h(const ampconv_view_t &v) {
@@ -717,9 +713,6 @@ int ampconv_bwd_edge_src_bf16(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t
   static const EdgeKernel kernels_tr[4] = {bwd_src_bf16_tr<false, false>, bwd_src_bf16_tr<true, false>, bwd_src_bf16_tr<false, true>,
                                            bwd_src_bf16_tr<true, true>};
   // developer switch: AMPCONV_BF16_SRC_TR=0 = the row-softmax kernel (DPP reductions), kept as the cross-check
-  static const bool tr = [] {
-    const char *e = getenv("AMPCONV_BF16_SRC_TR");
-    return !(e && e[0] == '0');
-  }();
+  static const bool tr = env_switch("AMPCONV_BF16_SRC_TR", true);
   return launch(a, L, D, H, tr ? kernels_tr : kernels, stream);
 }

@@ -671,11 +671,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 3) void bwd_src_f16x2(Args a) 
 typedef void (*EdgeKernel)(Args);
 // kernels[2 * half + full]
 int launch(Args &a, int L, bool half, EdgeKernel const (&kernels)[4], hipStream_t stream) {
-  const int64_t blocks = (a.n_units + kWavesPerBlock - 1) / kWavesPerBlock;
-  if (blocks > INT32_MAX) return AMPCONV_E_BADARG;
-  const dim3 grid((unsigned)blocks), block(64 * kWavesPerBlock);
-  kernels[2 * half + (L == kLmax)]<<<grid, block, 0, stream>>>(a);
-  return ampconv_launch_status();
+  return launch_wave_units(kernels[2 * half + (L == kLmax)], a, kWavesPerBlock, stream);
 }
 int launch_fwd(Args &a, int L, bool half, hipStream_t st) {
   static const EdgeKernel k[4] = {fwd_f16x2<false, false>, fwd_f16x2<true, false>, fwd_f16x2<false, true>, fwd_f16x2<true, true>};

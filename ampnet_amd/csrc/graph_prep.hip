@@ -313,10 +313,7 @@ extern "C" int ampconv_graph_build(const int64_t *edge_index, int64_t E, int64_t
                                    void *workspace, size_t workspace_bytes, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const bool plans = chunk > 0 && plan_dst && plan_src;
-  static const bool no_small = [] {
-    const char *e = getenv("AMPCONV_CSR_SMALL");
-    return e && e[0] == '0';
-  }();
+  static const bool no_small = !env_switch("AMPCONV_CSR_SMALL", true);
   if (!status) return AMPCONV_E_BADARG;
   hipError_t err = hipMemsetAsync(status, 0, 4 * sizeof(int32_t), stream);
   if (err != hipSuccess) return (int)err;

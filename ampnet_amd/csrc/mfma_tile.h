@@ -28,15 +28,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
-// 16-byte load of a streamed (gathered, read-once-per-edge) tile chunk.  AMPCONV_NT_LOADS: non-temporal hint.
+// 16-byte load of a streamed (gathered, read-once-per-edge) tile chunk
 template <typename P>
 __device__ __forceinline__ float4 stream_load4(const P *p) {
-#ifdef AMPCONV_NT_LOADS
-  const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(p));
-  return make_float4(v[0], v[1], v[2], v[3]);
-#else
   return *reinterpret_cast<const float4 *>(p);
-#endif
 }
 #define STREAM_LOAD4(p) stream_load4(p)
 

@@ -651,7 +651,8 @@ def test_softmax_stats_rejected_where_unsupported(dev):
 def test_batched_tail_kernels_vs_generic(shape, dev, monkeypatch):
     """The batched-tail kernels (fwd / dst / src `_t4`: tail tokens of four edges in one MFMA tile) on
     partially filled tails (L = 17..19), segment lengths of every residue mod 4, a hub and isolated
-    nodes, against the independent shape-generic kernels; and with the batching switched off."""
+    nodes, against the independent shape-generic kernels (with the batching switched off:
+    test_unbatched_mfma_kernels_match_batched)."""
     from ampnet_amd import AMPConv, graph_cache
     N, E, L, D, H = shape
     g = torch.Generator().manual_seed(L * 1000 + D)
@@ -1093,6 +1094,53 @@ np.savez(sys.argv[1], y=y.detach().cpu().numpy(), dx=x.grad.cpu().numpy(), gw=m.
         outs[name] = dict(np.load(path))
     for k in outs['nt4']:
         assert_close_scaled(outs['nt4'][k], outs['r1'][k], k + ' (4x4x1 tail vs 16x16x4 tiling)')
+
+
+@pytest.mark.parametrize('shape', [(260, 2600, 20, 64, 2), (260, 2600, 17, 64, 4)], ids=['L20_dh32', 'L17_dh16'])
+def test_unbatched_mfma_kernels_match_batched(shape, dev, tmp_path):
+    """The batched-tail kernels (default) against the same build with AMPCONV_{FWD,DST,SRC}_T4=0 (the plain one-edge-at-a-
+    time kernels fwd_mfma / bwd_dst_mfma / bwd_src_mfma), on the graph of test_batched_tail_kernels_vs_generic: a hub
+    destination and a hub source above the 64-edge chunk, segment lengths of every residue mod 4, a node that receives
+    nothing.  The switches are read once per process, so each setting runs in a child process."""
+    import subprocess
+    import sys
+    from conftest import ROOT
+    script = f'''
+import sys, numpy as np, torch
+sys.path.insert(0, {ROOT!r})
+from ampnet_amd import AMPConv
+N, E, L, D, H = (int(v) for v in sys.argv[2:7])
+dev = torch.device("cuda:0")
+g = torch.Generator().manual_seed(L * 1000 + D)
+ei = torch.randint(0, N, (2, E), generator=g)
+ei[1, :150] = 3                                   # hub destination
+ei[0, 150:300] = 5                                # hub source
+for k in range(1, 8):                             # nodes with exactly k in-edges and k out-edges
+    ei[1, 300 + 10 * k: 300 + 11 * k] = 100 + k
+    ei[1, ei[1] == 100 + k] = 100 + k
+    ei[0, 600 + 10 * k: 600 + 11 * k] = 200 + k
+ei[1, ei[1] == 7] = 8                             # node 7 receives nothing
+torch.manual_seed(L)
+layer = AMPConv(D, H).to(dev)
+with torch.no_grad():
+    layer.multi_head_attention.in_proj_bias.normal_(0, 0.2)
+x = torch.randn(N, L * D, generator=g).to(dev).requires_grad_(True)
+dy = torch.randn(N, L * D, generator=g).to(dev)
+y = layer(x, ei.to(dev))
+y.backward(dy)
+m = layer.multi_head_attention
+np.savez(sys.argv[1], y=y.detach().cpu().numpy(), dx=x.grad.cpu().numpy(), gw=m.in_proj_weight.grad.cpu().numpy(),
+         gb=m.in_proj_bias.grad.cpu().numpy(), gow=m.out_proj.weight.grad.cpu().numpy())
+'''
+    outs = {}
+    for name, extra in (('t4', {}), ('plain', {'AMPCONV_FWD_T4': '0', 'AMPCONV_DST_T4': '0', 'AMPCONV_SRC_T4': '0'})):
+        path = str(tmp_path / f'{name}.npz')
+        r = subprocess.run([sys.executable, '-c', script, path] + [str(v) for v in shape], env=dict(os.environ, **extra),
+                           timeout=600, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+        assert r.returncode == 0, r.stderr[-3000:]
+        outs[name] = dict(np.load(path))
+    for k in ('y', 'dx', 'gw', 'gb', 'gow'):
+        assert_close_scaled(outs['t4'][k], outs['plain'][k], k)
 
 
 def test_config2_literal_two_layers_cora_size(dev):
