@@ -161,6 +161,18 @@ __global__ __launch_bounds__(AMPCONV_WAVE) void bwd_dst_generic(BwdArgs a) {
   store_tile(tile_ptr<float>(a.dQ, r, h), dQs, L, dh, dhp, a.dQ.row_stride, a.scale, lane);
 }
 
+// sum += term with the rounding error of every addition carried in comp (Kahan)
+__device__ __forceinline__ void compensated_add(float &sum, float &comp, float term) {
+  const float y = term - comp, t = sum + y;
+  comp = (t - sum) - y;
+  sum = t;
+}
+
+// COMP: dK and dV are running sums over out-degree x L terms per element (this pass takes no long-segment plan, and
+// unlike O and dQ its outputs are sums, not means): plain fp32 addition loses 1e-4 of the result from ~800 out-edges
+// on (tests/test_gpu_edge_ladder.py), so every element carries its compensation in a second tile.  Without it: the
+// shapes whose two extra tiles do not fit the LDS.
+template <bool COMP>
 __global__ __launch_bounds__(AMPCONV_WAVE) void bwd_src_generic(BwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int lane = threadIdx.x;
@@ -168,12 +180,16 @@ __global__ __launch_bounds__(AMPCONV_WAVE) void bwd_src_generic(BwdArgs a) {
   const int h = blockIdx.x - s * a.H;
   const int L = a.L, dh = a.dh, dhp = a.dhp, T = L * dhp;
   float *Ks = lds, *Vs = Ks + T, *dKs = Vs + T, *dVs = dKs + T, *Qs = dVs + T, *dOs = Qs + T,
-        *P = dOs + T, *dS = P + L;
+        *P = dOs + T, *dS = P + L, *cKs = dS + L, *cVs = cKs + T;      // (cKs, cVs: COMP only)
   const int beg = a.ptr[s], end = a.ptr[s + 1];
   load_tile(Ks, tile_ptr<const float>(a.K, s, h), L, dh, dhp, a.K.row_stride, 1.f, lane);
   load_tile(Vs, tile_ptr<const float>(a.V, s, h), L, dh, dhp, a.V.row_stride, 1.f, lane);
   zero_tile(dKs, T, lane);
   zero_tile(dVs, T, lane);
+  if (COMP) {
+    zero_tile(cKs, T, lane);
+    zero_tile(cVs, T, lane);
+  }
   for (int p = beg; p < end; ++p) {
     const int64_t d = a.idx[p];
     const float inv = a.cinv[p];
@@ -186,8 +202,13 @@ __global__ __launch_bounds__(AMPCONV_WAVE) void bwd_src_generic(BwdArgs a) {
       dsoftmax_row(dOs + i * dhp, Vs, P, dS, L, dh, dhp, lane);
       for (int idx = lane; idx < L * dh; idx += AMPCONV_WAVE) {
         int j = idx / dh, c = idx - j * dh;
-        dVs[j * dhp + c] = fmaf(P[j], dOs[i * dhp + c], dVs[j * dhp + c]);
-        dKs[j * dhp + c] = fmaf(dS[j], Qs[i * dhp + c], dKs[j * dhp + c]);   // Qs carries the scale
+        if (COMP) {
+          compensated_add(dVs[j * dhp + c], cVs[j * dhp + c], P[j] * dOs[i * dhp + c]);
+          compensated_add(dKs[j * dhp + c], cKs[j * dhp + c], dS[j] * Qs[i * dhp + c]);   // Qs carries the scale
+        } else {
+          dVs[j * dhp + c] = fmaf(P[j], dOs[i * dhp + c], dVs[j * dhp + c]);
+          dKs[j * dhp + c] = fmaf(dS[j], Qs[i * dhp + c], dKs[j * dhp + c]);   // Qs carries the scale
+        }
       }
       __syncthreads();
     }
@@ -197,8 +218,6 @@ __global__ __launch_bounds__(AMPCONV_WAVE) void bwd_src_generic(BwdArgs a) {
   store_tile(tile_ptr<float>(a.dV, s, h), dVs, L, dh, dhp, a.dV.row_stride, 1.f, lane);
 }
 
-// attn_output_weights[e] = mean over heads of P (torch functional.py:6604-6606),
-// one wavefront per edge in ORIGINAL edge order.
 __global__ __launch_bounds__(AMPCONV_WAVE) void attn_weights_generic(WArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int lane = threadIdx.x;
@@ -301,9 +320,15 @@ int ampconv_bwd_edge_src_generic(ampconv_view_t Q, ampconv_view_t K, ampconv_vie
   a.ptr = cscptr; a.idx = crow; a.cinv = cinv;
   a.L = L; a.dh = D / H; a.dhp = pad_odd(a.dh); a.H = H;
   a.scale = 1.f / sqrtf((float)a.dh);
-  size_t lds = ((size_t)6 * L * a.dhp + 2 * L) * sizeof(float);
-  if (int rc = set_lds(bwd_src_generic, lds)) return rc;
-  bwd_src_generic<<<(unsigned)(n_src * H), AMPCONV_WAVE, lds, stream>>>(a);
+  const size_t plain = ((size_t)6 * L * a.dhp + 2 * L) * sizeof(float);
+  const size_t comp = plain + (size_t)2 * L * a.dhp * sizeof(float);      // the compensation tiles of dK and dV
+  if (comp <= kMaxLds) {
+    if (int rc = set_lds(bwd_src_generic<true>, comp)) return rc;
+    bwd_src_generic<true><<<(unsigned)(n_src * H), AMPCONV_WAVE, comp, stream>>>(a);
+  } else {
+    if (int rc = set_lds(bwd_src_generic<false>, plain)) return rc;
+    bwd_src_generic<false><<<(unsigned)(n_src * H), AMPCONV_WAVE, plain, stream>>>(a);
+  }
   return ampconv_launch_status();
 }
 

@@ -597,9 +597,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 3) void bwd_src_f16x2(Args a) 
       for (int mt = 0; mt < 2; ++mt) {
 #pragma unroll
         for (int q = 0; q < (mt == 0 ? 4 : 1); ++q) {
-          const float ls = mt == 0 ? l0[q] : l1, dl = mt == 0 ? d0[q] : d1;
-          // (rows of tokens >= L have no statistics: their weights are zero, not exp2 of whatever the buffer holds)
+          // (rows of tokens >= L have no statistics: their weights are zero, not exp2 of whatever the buffer holds --
+          // which the destination pass never wrote and may be a NaN or an infinity, so it is not read into ls / dl)
           const bool vr = FULL || (mt == 0 ? 4 * g + q : 16 + g) < L;
+          const float ls = !vr ? 0.f : mt == 0 ? l0[q] : l1, dl = !vr ? 0.f : mt == 0 ? d0[q] : d1;
           const float s0 = (v0 && vr) ? S[mt][0][q] : kMasked, s1 = (v1 && vr) ? S[mt][1][q] : kMasked;
           const float p0 = fast_exp2(fmaf(s0, sc, -ls)), p1 = fast_exp2(fmaf(s1, sc, -ls));
           S[mt][0][q] = p0 * kPScale;

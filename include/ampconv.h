@@ -128,7 +128,12 @@ int ampconv_active_nodes(const int32_t *rowptr, const int32_t *cscptr, int64_t N
  * partial tiles (fixed order: bitwise reproducible).  plan = int32 header {n_chunks, chunk, 0, 0}
  * followed by 16-byte descriptors; the caller reads header[0] back once (n_chunks), sizes
  * hub_ws with ampconv_hub_workspace_bytes and passes both to the edge calls (plan = NULL or
- * n_chunks = 0: no splitting).  n_tiles = 1 (forward, dst pass) or 2 (src pass: dK and dV).  */
+ * n_chunks = 0: no splitting).  n_tiles = 1 (forward, dst pass) or 2 (src pass: dK and dV).
+ * A plan passed to an edge call must have been built over EXACTLY the rows the call covers --
+ * ampconv_hub_plan(ptr, n_rows, ...) for a call with that n_rows (n_src), over the same ptr: the passes write the output
+ * row of every long row the plan names, whatever their own row count is, so a plan over more rows overwrites rows behind
+ * n_rows, and one over fewer leaves long rows unwritten.  (The row count of a plan lives in device memory only; the
+ * entry points cannot check it without a read-back and do not.)  */
 size_t ampconv_hub_plan_bytes(int64_t E, int chunk);
 int ampconv_hub_plan(const int32_t *ptr, int64_t N, int64_t E, int chunk, void *plan, void *stream);
 size_t ampconv_hub_workspace_bytes(int64_t n_chunks, int L, int D, int n_tiles);
@@ -264,7 +269,9 @@ int ampconv_bwd_edge_src_planes(ampconv_view_t Q, ampconv_view_t K, ampconv_view
  * the vector instructions of the bound-free kernels behind the fp32 entry points, which split into three bf16 planes).
  * dObar is the gradient of the mean as in the fp32 entry points (the passes apply 1 / in-degree; `cinv` as in
  * ampconv_bwd_edge_src).  Softmax statistics: ampconv_softmax_stats_bytes(E, L, D, H, AMPCONV_F32) bytes, REQUIRED by
- * the source pass, delta in the units of the scaled dObar V^T product.  out_absmax as above.  Same accuracy class as the
+ * the source pass, delta in the units of the scaled dObar V^T product -- E * H * 32 * ceil(L / 16) floats, which is also
+ * what these entry points need at the few shapes they serve where that function answers 0 because the fp32 entry points
+ * keep no statistics there (the short-sequence shapes, e.g. L <= 4 at D = 64, H = 1).  out_absmax as above.  Same accuracy class as the
  * fp32 kernels on tensors whose rows lie within ~2^12 of the tensor's maximum (see ampconv_planes_supported).  */
 int ampconv_scaled_supported(int L, int D, int H);
 int ampconv_fwd_edge_scaled(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V,

@@ -147,3 +147,47 @@ def test_layout_helper_places_without_overlap_and_with_the_alignment_it_names():
             assert out.unwritten() == x.size - L * H * dh and out.unwritten(slice(2, 3)) == 0
             a = el.alignment_bytes([view], esize)
             assert a == {'pad8': 8, 'pad4': 4}.get(layout, 16), (layout, a)
+
+
+@pytest.mark.parametrize('chunk,E', [(64, 3926), (128, 7638)])
+def test_ladder_graph_holds_the_segment_lengths_it_is_for(chunk, E):
+    """tests/edge_runner.py: graph('L', chunk), the graph of tests/test_gpu_edge_ladder.py.  Both degree sequences, the
+    edge count, 63 chunks on either side in rows of 2, 3, 4, 5, 9, 13 and 17, self-loops and multi-edges; and
+    er.csr_of on it is a STABLE sort by destination."""
+    import edge_runner as rn
+    c = chunk
+    want = list(range(21)) + [c - 1, c, c + 1, 2 * c - 1, 2 * c, 2 * c + 1, 3 * c - 1, 3 * c, 3 * c + 1,
+                              4 * c + 1, 8 * c + 1, 12 * c + 1, 16 * c + 1, 0, 0, 0]
+    g = rn.graph('L', chunk)
+    assert (g.N, g.n_rows, g.E) == (37, 37, E)
+    assert g.indeg.tolist() == want == rn.ladder_degrees(chunk).tolist()
+    assert sorted(g.outdeg.tolist()) == sorted(want) and g.outdeg.tolist() != want       # the same multiset, moved
+    assert not g.indeg[34:].any() and not g.outdeg[34:].any()                             # three isolated nodes
+    for deg in (g.indeg, g.outdeg):
+        per_row = rn.chunks_per_row(deg, chunk)
+        assert per_row.sum() == rn.LADDER_CHUNKS == 63 and set(per_row.tolist()) == {2, 3, 4, 5, 9, 13, 17}
+        assert (deg == chunk).sum() == 1 and len(per_row) == 11                           # exactly `chunk` edges: not cut
+    loops = int((g.src == g.dst).sum())
+    pairs = np.unique(np.stack([g.src, g.dst]), axis=1).shape[1]
+    print(f'chunk {chunk}: {loops} self-loops, {g.E - pairs} repeated edges')
+    assert loops >= 100 and pairs < g.E
+    # csr_of: the row pointers are the running in-degrees; equal destinations keep the order they came in, also when the
+    # edge list arrives shuffled
+    assert np.array_equal(g.rowptr, np.concatenate([[0], np.cumsum(want)])) and np.array_equal(g.col, g.src)
+    perm = np.random.default_rng(3).permutation(g.E)
+    rowptr, col = er.csr_of(g.src[perm], g.dst[perm], g.N)
+    assert np.array_equal(rowptr, g.rowptr)
+    assert np.array_equal(col, g.src[perm][np.lexsort((np.arange(g.E), g.dst[perm]))])
+    for r in (5, 22, 33):                                    # row r holds the sources of its edges in arrival order
+        assert np.array_equal(col[rowptr[r]:rowptr[r + 1]], g.src[perm][g.dst[perm] == r])
+
+
+def test_header_rule_agrees_with_the_family_table():
+    """edge_runner.header_rule (the rule of ANY shape, which the token-count sweep uses) gives every listed shape the
+    rule the table lists for it."""
+    import edge_runner as rn
+    for (dtype, shape), rule in rn.TABLE.items():
+        assert rn.header_rule(dtype, shape) is rule, (dtype, shape)
+    assert rn.header_rule(rn.F32, (4, 32, 4), small=False) is rn._ONE_WAVE
+    assert rn.header_rule(rn.F32, (4, 64, 1)) is rn._SMALL_V2 and rn.header_rule(rn.F32, (5, 64, 1)) is rn._PER_UNIT
+    assert rn.header_rule(rn.BF16, (20, 96, 1)) is None
