@@ -6,10 +6,10 @@ Host side: Python on PyTorch-ROCm (device memory, streams, torch.distributed).
 Compute: libampconv.so, hand-written HIP for gfx950 behind the C ABI of
 include/ampconv.h.  No CPU fallback.
 """
-from .conv import AMPConv, InvalidConfiguration
+from .conv import AMPConv, GCNConv, InvalidConfiguration
 from .graph import EdgeCSR, graph_cache
 from . import distributed
-from .module import AMPGCN, FeatureTokens
+from .module import AMPGCN, GCN, FeatureTokens
 from .sampler import GraphSAINTRandomWalkSampler
 from .partitioned import NodePartition, PartitionedAMPConv
 from .graphed import GraphedAMPConv
@@ -19,9 +19,10 @@ from .head import HeadMetrics, classifier_head, saint_nll_loss
 from .norm import NormTokenReadout, TokenLayerNorm, norm_act_dropout, norm_act_dropout_pool
 from .optim import FusedAdam
 from .stats import TensorStats, tensor_stats
+from .gcn import gcn_aggregate, gcn_input_linear, gcn_norm
 
 __all__ = ['AMPConv', 'InvalidConfiguration', 'EdgeCSR', 'graph_cache', 'distributed', 'AMPGCN', 'FeatureTokens',
            'GraphSAINTRandomWalkSampler', 'NodePartition', 'PartitionedAMPConv', 'GraphedAMPConv', 'AttentionHeatmap', 'top_features',
            'ActDropout', 'TokenReadout', 'act_dropout', 'act_dropout_pool', 'HeadMetrics', 'classifier_head', 'saint_nll_loss',
            'NormTokenReadout', 'TokenLayerNorm', 'norm_act_dropout', 'norm_act_dropout_pool', 'FusedAdam',
-           'TensorStats', 'tensor_stats']
+           'TensorStats', 'tensor_stats', 'GCNConv', 'GCN', 'gcn_norm', 'gcn_aggregate', 'gcn_input_linear']

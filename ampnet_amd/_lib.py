@@ -61,6 +61,7 @@ STATS_CHUNK = 4096        # AMPCONV_STATS_CHUNK: elements one workgroup handles 
 STATS_MAX_BINS = 2048     # AMPCONV_STATS_MAX_BINS
 STATS_MAX_RANKS = 4       # AMPCONV_STATS_MAX_RANKS: order statistics per call
 STATS_RECORD_BYTES = 88   # sizeof(ampconv_stats_record_t)
+GCN_LONG_SEGMENT = 256    # AMPCONV_GCN_LONG_SEGMENT: a CSR/CSC segment from this length on is summed by whole workgroups
 
 # name -> (restype, argtypes); mirrors include/ampconv.h one to one
 SIGNATURES = {
@@ -163,6 +164,15 @@ SIGNATURES = {
     'ampconv_stats_histogram': (_i32, [ctypes.POINTER(StatsTensor), _i32, _i32, _vp, _vp, _vp, _vp]),
     'ampconv_stats_select': (_i32, [ctypes.POINTER(StatsTensor), _i32, ctypes.POINTER(ctypes.c_double), _i32, _vp, _vp,
                                     _vp, _sz, _vp]),
+    'ampconv_gcn_norm': (_i32, [_vp, _vp, _i64, _i32, ctypes.c_float, _vp, _vp]),
+    'ampconv_gcn_aggregate_workspace_bytes': (_sz, [_i64, _i64, _i32]),
+    'ampconv_gcn_aggregate': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, ctypes.c_float, _vp, _vp, _i64, _i64, _i64, _vp,
+                                     _sz, _vp]),
+    'ampconv_gcn_colsum_workspace_bytes': (_sz, [_i64, _i32]),
+    'ampconv_gcn_colsum': (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _sz, _vp]),
+    'ampconv_gcn_input_workspace_bytes': (_sz, [_i64, _i64, _i32]),
+    'ampconv_gcn_input_fwd': (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _sz, _vp]),
+    'ampconv_gcn_input_bwd': (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -1,3 +1,4 @@
 from .amp_gcn import AMPGCN, FeatureTokens
+from .gcn import GCN
 
-__all__ = ['AMPGCN', 'FeatureTokens']
+__all__ = ['AMPGCN', 'FeatureTokens', 'GCN']

@@ -6,6 +6,10 @@ node_norm-weighted NLL.  Everything between the data and the loss runs on the GP
 
     python examples/train_graphsaint.py [--epochs 3] [--dropout 0.1 --fused-glue] [--fused-head] [--layer-norm]
                                         [--fused-adam [--clip M] [--track-grad-norm]] [--diagnostics K [--diag-dir DIR]]
+                                        [--model gcn [--gcn-input {embedded,zscore,raw}] [--hidden 16]]
+
+--model gcn trains the baseline behind the reference's `TRAIN_AMPCONV = False` (:27,58-75): the 2-layer GCN of
+src/ampnet/module/gcn_classifier.py on the same batches, optimiser, schedule and loss.
 """
 import argparse
 import os
@@ -18,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
-from ampnet_amd import AMPGCN, FusedAdam, GraphSAINTRandomWalkSampler, HeadMetrics  # noqa: E402
+from ampnet_amd import AMPGCN, GCN, FusedAdam, GraphSAINTRandomWalkSampler, HeadMetrics  # noqa: E402
 
 
 def synthetic_cora(device, n=2708, f=1433, classes=7, seed=1):
@@ -66,8 +70,14 @@ def report(epoch, queued, model, diag_dir):
         model.visualize_activations(diag_dir, None, epoch, i, stats=a)
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument('--model', choices=('ampgcn', 'gcn'), default='ampgcn',
+                    help="gcn: the reference's baseline (TRAIN_AMPCONV = False): GCN(hidden) on the HIP GCN kernels")
+    ap.add_argument('--gcn-input', choices=('embedded', 'zscore', 'raw'), default='embedded',
+                    help="with --model gcn: the first layer's input -- the reference's cat(embedding table, z-scored value) "
+                         '(never formed in memory), the z-scored features alone, or the raw features of the demos')
+    ap.add_argument('--hidden', type=int, default=16, help='with --model gcn: hidden_dim (gcn_classifier.py:21)')
     ap.add_argument('--epochs', type=int, default=3)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--class-defaults', action='store_true',
@@ -96,19 +106,28 @@ def main():
                          "activation_stats); they are read and printed with the epoch's one read-back")
     ap.add_argument('--diag-dir', default=None, metavar='DIR',
                     help="with --diagnostics: write the reference's three figures for the last queued batch of every epoch there")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.diag_dir is not None and args.diagnostics <= 0:
         ap.error('--diag-dir needs --diagnostics K')
     if (args.clip is not None or args.track_grad_norm) and not args.fused_adam:
         ap.error('--clip and --track-grad-norm need --fused-adam')
+    if args.model == 'gcn' and (args.layer_norm or args.diagnostics > 0 or args.class_defaults):
+        ap.error('--layer-norm, --diagnostics and --class-defaults belong to --model ampgcn')
     device = torch.device('cuda:0')
     torch.manual_seed(1)
     data = synthetic_cora(device)
     D, H, L = (100, 2, 40) if args.class_defaults else (128, 4, 20)
-    model = AMPGCN(device=device, embedding_dim=D, num_heads=H, num_node_features=1433, num_sampled_vectors=L,
-                   output_dim=7, softmax_out=True, feat_emb_dim=D - 1, val_emb_dim=1, dropout_rate=args.dropout,
-                   dropout_adj_rate=0.0, fused_glue=args.fused_glue, fused_head=args.fused_head,
-                   layer_norm=args.layer_norm).to(device)
+    if args.model == 'gcn':
+        model = GCN(device=device, num_node_features=1433, hidden_dim=args.hidden, num_sampled_vectors=1433, output_dim=7,
+                    softmax_out=True, feat_emb_dim=99, val_emb_dim=1, dropout_rate=args.dropout, dropout_adj_rate=0.0,
+                    input=args.gcn_input, fused_glue=args.fused_glue, fused_head=args.fused_head).to(device)
+        what = f'sampler + 2 GCNConv layers ({args.gcn_input} input) fwd+bwd + Adam'
+    else:
+        model = AMPGCN(device=device, embedding_dim=D, num_heads=H, num_node_features=1433, num_sampled_vectors=L,
+                       output_dim=7, softmax_out=True, feat_emb_dim=D - 1, val_emb_dim=1, dropout_rate=args.dropout,
+                       dropout_adj_rate=0.0, fused_glue=args.fused_glue, fused_head=args.fused_head,
+                       layer_norm=args.layer_norm).to(device)
+        what = 'sampler + 2 AMPConv layers fwd+bwd + Adam'
     loader = GraphSAINTRandomWalkSampler(data, batch_size=8, walk_length=150, num_steps=args.steps,
                                          sample_coverage=20, seed=1)
     if args.fused_adam:
@@ -166,7 +185,7 @@ def main():
         report(epoch, queued, model, args.diag_dir)
         print(f'epoch {epoch}: train loss {tot / cnt:.4f}  train acc {correct / cnt:.3f}{extra}  '
               f'({time.time() - t0:.1f} s; this epoch {time.time() - te:.3f} s = {1e3 * (time.time() - te) / cnt:.2f} ms '
-              f'per sampled batch, sampler + 2 AMPConv layers fwd+bwd + Adam)', flush=True)
+              f'per sampled batch, {what})', flush=True)
     model.eval()
     with torch.no_grad():
         out = model(data)                                                   # full-graph eval (:159-163)

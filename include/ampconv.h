@@ -788,6 +788,67 @@ int ampconv_stats_select(const ampconv_stats_tensor_t *t, int n, const double *q
                          const ampconv_stats_record_t *records, float *out, void *workspace, size_t workspace_bytes,
                          void *stream);
 
+/* ---- GCN baseline (csrc/gcn.hip; pure additions, the ABI number stays 111) -------------------------------------------
+ * Reference: the other side of every training script's TRAIN_AMPCONV switch, src/ampnet/module/gcn_classifier.py:17-109:
+ * two PyG GCNConv layers behind cat(feature_embedding_table.weight, zscore(x)[n]) per node.  PyG is not a dependency:
+ * the semantics below restate PyG 2.0-2.1's gcn_norm / GCNConv and ARE the specification (GCN baseline).
+ * fp32 throughout, no floating-point atomics, every sum in a fixed order: every output has the same bits on every launch.
+ * (ptr, idx) is a sorted adjacency: segment n = idx[ptr[n] .. ptr[n + 1]) -- the destination-sorted CSR (rowptr, col) for
+ * the forward operator, the source-sorted CSC (cscptr, crow) for the transposed one.  fill = 2 (improved) or 1.
+ *   gcn_norm:  deg[n] = (entries of segment n with idx != n) + fill   with add_self_loops (every loop in the input is
+ *              dropped, one loop of weight fill is added per node), else the segment length;
+ *              dinv[n] = deg[n]^-1/2, 0 where deg[n] == 0.  Computed on the CSR; the same dinv serves both directions.
+ *   gcn_aggregate:  keep(p) = !add_self_loops || idx[p] != n
+ *              out[n, c] = dinv[n] (sum_{p in segment n, keep(p)} dinv[idx[p]] h[idx[p], c]
+ *                                   + (add_self_loops ? fill dinv[n] h[n, c] : 0)) + (bias ? bias[c] : 0)
+ *              The edge weight dinv[src] w dinv[dst] is symmetric in its two factors, so the transposed operator (the
+ *              gradient to h) is the same call on the CSC with bias = NULL; no E-sized weight array exists.
+ *              h [N, C] with row stride ld_h >= C, out likewise with ld_out; any C >= 1; columns >= C of a wider buffer
+ *              are neither read nor written.  16-byte loads and stores where ld_h and ld_out are multiples of 4 and both
+ *              bases are 16-byte aligned, 4-byte ones otherwise (same bits either way).
+ *              MAPPING.  A row is owned by 4 edge slots x Q column quads of a wave (Q = the power of two that covers
+ *              ceil(C / 4), at most 16: wider rows loop over column chunks), so 64 / (4 Q) rows are in flight per wave
+ *              instruction.  A slot adds its entries in ascending order, the slots combine in a fixed xor order.  A segment
+ *              of AMPCONV_GCN_LONG_SEGMENT entries or more is not walked by its lanes when `workspace` is given: it is cut
+ *              into parts of AMPCONV_GCN_PART entries, a workgroup sums one part (256 / Q slots, ordered LDS combine) into
+ *              a partial row, and a last kernel adds a row's partial rows in part order.  workspace NULL (what a caller may
+ *              pass when it knows that no segment is long; required size 0 when E < AMPCONV_GCN_LONG_SEGMENT): every
+ *              segment is walked by its lane group -- correct for any length, slow for long ones.
+ *   gcn_colsum:  out[c] = sum_n g[n, c] (row stride ld): at most 1024 chunks of consecutive rows, each in ascending
+ *              order, then the chunks in ascending order (the bias gradient).
+ *   gcn_input_fwd / _bwd: the first layer's linear map over the embedded input WITHOUT forming it.  Token f of node n is
+ *              cat(table[f, :De], z[n, f]), z = (x - mean) inv_std (the expression of ampconv_feat_build; mean, inv_std of
+ *              ampconv_feat_zscore_stats); with W [C, F (De + 1)] viewed as [C, F, De + 1]:
+ *                  h[n, j] = sum_f z[n, f] W[j, f, De] + c[j],     c[j] = sum_f sum_k table[f, k] W[j, f, k]
+ *              De == 0 with table == NULL is the plain z-scored input (c = 0); mean == inv_std == NULL (De == 0 only)
+ *              the raw one, z = x.  mean inv_std is never folded into the weights.  x [N, F] contiguous, h [N, C] with row
+ *              stride ld_h.  Backward, from g = dL/dh [N, C] (row stride ld_g) and s[j] = sum_n g[n, j]:
+ *                  dW[j, f, De] = sum_n z[n, f] g[n, j]   (at most 64 chunks of rows, ascending inside and across)
+ *                  dW[j, f, k < De] = s[j] table[f, k];    dtable[f, k] = sum_j s[j] W[j, f, k]   (ascending j)
+ *              dW [C, F (De + 1)] and dtable [F, De] (NULL with De == 0) are written whole.  No gradient to x.
+ *              workspace: ampconv_gcn_input_workspace_bytes(N, F, C) bytes, 16-byte aligned, need not be zeroed.
+ * ERRORS: a missing pointer, C < 1, a row stride below C, negative sizes, N or E above 2^31 - 1, a pointer that is not
+ * 4-byte aligned, a table without De or De without a table or without mean: AMPCONV_E_BADARG; a short or misaligned
+ * workspace: AMPCONV_E_WORKSPACE -- nothing is launched.  N == 0 succeeds.  */
+#define AMPCONV_GCN_LONG_SEGMENT 256
+#define AMPCONV_GCN_PART 2048
+int ampconv_gcn_norm(const int32_t *ptr, const int32_t *idx, int64_t N, int add_self_loops, float fill, float *dinv,
+                     void *stream);
+size_t ampconv_gcn_aggregate_workspace_bytes(int64_t N, int64_t E, int C);
+int ampconv_gcn_aggregate(const float *h, int64_t ld_h, int C, const int32_t *ptr, const int32_t *idx,
+                          const float *dinv, int add_self_loops, float fill, const float *bias, float *out,
+                          int64_t ld_out, int64_t N, int64_t E, void *workspace, size_t workspace_bytes, void *stream);
+size_t ampconv_gcn_colsum_workspace_bytes(int64_t N, int C);
+int ampconv_gcn_colsum(const float *g, int64_t ld, int64_t N, int C, float *out, void *workspace,
+                       size_t workspace_bytes, void *stream);
+size_t ampconv_gcn_input_workspace_bytes(int64_t N, int64_t F, int C);
+int ampconv_gcn_input_fwd(const float *x, int64_t N, int64_t F, const float *mean, const float *inv_std, const float *W,
+                          const float *table, int De, int C, float *h, int64_t ld_h, void *workspace,
+                          size_t workspace_bytes, void *stream);
+int ampconv_gcn_input_bwd(const float *x, int64_t N, int64_t F, const float *mean, const float *inv_std, const float *W,
+                          const float *table, int De, int C, const float *g, int64_t ld_g, float *dW, float *dtable,
+                          void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
