@@ -47,6 +47,13 @@ class AdamTensor(ctypes.Structure):
                 ('numel', ctypes.c_int64), ('step_size', ctypes.c_float), ('inv_bc2_sqrt', ctypes.c_float)]
 
 
+class AdamMixedTensor(ctypes.Structure):
+    """ampconv_adam_mixed_tensor_t: one tensor of ampconv_adam_mixed_step / ampconv_adam_mixed_grad_norm (64 bytes)."""
+    _fields_ = [('p', ctypes.c_void_p), ('g', ctypes.c_void_p), ('m', ctypes.c_void_p), ('v', ctypes.c_void_p),
+                ('master', ctypes.c_void_p), ('numel', ctypes.c_int64), ('step_size', ctypes.c_float),
+                ('inv_bc2_sqrt', ctypes.c_float), ('p_dtype', ctypes.c_int32), ('g_dtype', ctypes.c_int32)]
+
+
 ADAM_MAX_TENSORS = 24     # AMPCONV_ADAM_MAX_TENSORS: descriptors per launch
 ADAM_CHUNK = 1024         # AMPCONV_ADAM_CHUNK: elements per workgroup
 
@@ -103,6 +110,8 @@ SIGNATURES = {
     'ampconv_feat_sample_present': (_i32, [_vp, _i64, _i32, _i32, ctypes.c_uint64, _vp, _vp, _vp]),
     'ampconv_feat_build': (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     'ampconv_feat_table_grad': (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    'ampconv_feat_build_as': (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp]),
+    'ampconv_feat_table_grad_from': (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp]),
     'ampconv_proj_supported': (_i32, [_i32, _i32, _i32]),
     'ampconv_proj_weight_image_bytes': (_sz, [_i32, _i32, _i32]),
     'ampconv_proj_weight_image': (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _i32, _vp]),
@@ -159,6 +168,10 @@ SIGNATURES = {
     'ampconv_adam_grad_norm': (_i32, [ctypes.POINTER(AdamTensor), _i32, ctypes.c_float, _vp, _vp, _sz, _vp]),
     'ampconv_adam_step': (_i32, [ctypes.POINTER(AdamTensor), _i32, ctypes.c_float, ctypes.c_double, ctypes.c_double,
                                  ctypes.c_float, ctypes.c_float, _i32, ctypes.c_float, _vp, ctypes.c_float, _vp]),
+    'ampconv_adam_mixed_workspace_bytes': (_sz, [ctypes.POINTER(AdamMixedTensor), _i32]),
+    'ampconv_adam_mixed_grad_norm': (_i32, [ctypes.POINTER(AdamMixedTensor), _i32, ctypes.c_float, _vp, _vp, _sz, _vp]),
+    'ampconv_adam_mixed_step': (_i32, [ctypes.POINTER(AdamMixedTensor), _i32, ctypes.c_float, ctypes.c_double, ctypes.c_double,
+                                       ctypes.c_float, ctypes.c_float, _i32, ctypes.c_float, _vp, ctypes.c_float, _vp]),
     'ampconv_stats_workspace_bytes': (_sz, [ctypes.POINTER(StatsTensor), _i32]),
     'ampconv_stats_moments': (_i32, [ctypes.POINTER(StatsTensor), _i32, _vp, _vp, _sz, _vp]),
     'ampconv_stats_histogram': (_i32, [ctypes.POINTER(StatsTensor), _i32, _i32, _vp, _vp, _vp, _vp]),

@@ -73,32 +73,35 @@ __global__ __launch_bounds__(64) void sample_present_kernel(const float *__restr
   }
 }
 
-// out[n, l, :De] = table[idx[n,l], :], out[n, l, De] = (x[n, idx] - mean) * inv_std
+// out[n, l, :De] = table[idx[n,l], :], out[n, l, De] = (x[n, idx] - mean) * inv_std; T = float or __bf16 (the fp32 value
+// rounded to nearest even), one element per lane whatever the row width
+template <typename T>
 __global__ void build_tokens_kernel(const float *__restrict__ x, const float *__restrict__ mean,
                                     const float *__restrict__ inv_std, const int32_t *__restrict__ idx,
                                     const float *__restrict__ table, int64_t NL, int F, int L, int De,
-                                    float *__restrict__ out) {
+                                    T *__restrict__ out) {
   const int64_t t = blockIdx.x;                        // token (n, l)
   const int f = idx[t];
   const int64_t n = t / L;
-  float *o = out + t * (int64_t)(De + 1);
+  T *o = out + t * (int64_t)(De + 1);
   if (f < 0) {
-    for (int c = threadIdx.x; c <= De; c += blockDim.x) o[c] = 0.f;
+    for (int c = threadIdx.x; c <= De; c += blockDim.x) o[c] = (T)0.f;
     return;
   }
-  for (int c = threadIdx.x; c < De; c += blockDim.x) o[c] = table[(int64_t)f * De + c];
-  if (threadIdx.x == 0) o[De] = (x[n * (int64_t)F + f] - mean[f]) * inv_std[f];
+  for (int c = threadIdx.x; c < De; c += blockDim.x) o[c] = (T)table[(int64_t)f * De + c];
+  if (threadIdx.x == 0) o[De] = (T)((x[n * (int64_t)F + f] - mean[f]) * inv_std[f]);
 }
 
 // dtable[f, :] += dout[n, l, :De] for every token with idx == f (float atomics: order of the adds,
-// hence the last bits, may differ run to run -- as with torch's own embedding backward)
-__global__ void table_grad_kernel(const float *__restrict__ dout, const int32_t *__restrict__ idx, int De,
+// hence the last bits, may differ run to run -- as with torch's own embedding backward); a bf16 dout is widened first
+template <typename T>
+__global__ void table_grad_kernel(const T *__restrict__ dout, const int32_t *__restrict__ idx, int De,
                                   float *__restrict__ dtable) {
   const int64_t t = blockIdx.x;
   const int f = idx[t];
   if (f < 0) return;
-  const float *g = dout + t * (int64_t)(De + 1);
-  for (int c = threadIdx.x; c < De; c += blockDim.x) atomicAdd(dtable + (int64_t)f * De + c, g[c]);
+  const T *g = dout + t * (int64_t)(De + 1);
+  for (int c = threadIdx.x; c < De; c += blockDim.x) atomicAdd(dtable + (int64_t)f * De + c, (float)g[c]);
 }
 
 }  // namespace
@@ -121,23 +124,43 @@ extern "C" int ampconv_feat_sample_present(const float *x, int64_t N, int F, int
   return ampconv_launch_status();
 }
 
-extern "C" int ampconv_feat_build(const float *x, const float *mean, const float *inv_std, const int32_t *idx,
-                                  const float *table, int64_t N, int F, int L, int De, float *out,
-                                  void *stream) {
+extern "C" int ampconv_feat_build_as(const float *x, const float *mean, const float *inv_std, const int32_t *idx,
+                                     const float *table, int64_t N, int F, int L, int De, void *out, int dtype,
+                                     void *stream) {
+  if (dtype != AMPCONV_F32 && dtype != AMPCONV_BF16) return AMPCONV_E_DTYPE;
   if (!x || !mean || !inv_std || !idx || !table || !out || N <= 0 || F <= 0 || L <= 0 || De < 0)
     return AMPCONV_E_BADARG;
   if (N * L > INT32_MAX) return AMPCONV_E_BADARG;
-  build_tokens_kernel<<<(unsigned)(N * L), 64, 0, (hipStream_t)stream>>>(x, mean, inv_std, idx, table, N * L, F,
-                                                                        L, De, out);
+  const unsigned grid = (unsigned)(N * L);
+  if (dtype == AMPCONV_BF16)
+    build_tokens_kernel<<<grid, 64, 0, (hipStream_t)stream>>>(x, mean, inv_std, idx, table, N * L, F, L, De, (__bf16 *)out);
+  else
+    build_tokens_kernel<<<grid, 64, 0, (hipStream_t)stream>>>(x, mean, inv_std, idx, table, N * L, F, L, De, (float *)out);
+  return ampconv_launch_status();
+}
+
+extern "C" int ampconv_feat_build(const float *x, const float *mean, const float *inv_std, const int32_t *idx,
+                                  const float *table, int64_t N, int F, int L, int De, float *out,
+                                  void *stream) {
+  return ampconv_feat_build_as(x, mean, inv_std, idx, table, N, F, L, De, out, AMPCONV_F32, stream);
+}
+
+extern "C" int ampconv_feat_table_grad_from(const void *dout, const int32_t *idx, int64_t N, int L, int De, int F,
+                                            float *dtable, int dtype, void *stream) {
+  if (dtype != AMPCONV_F32 && dtype != AMPCONV_BF16) return AMPCONV_E_DTYPE;
+  if (!dout || !idx || !dtable || N <= 0 || L <= 0 || De <= 0 || F <= 0 || N * L > INT32_MAX)
+    return AMPCONV_E_BADARG;
+  hipError_t e = hipMemsetAsync(dtable, 0, sizeof(float) * (size_t)F * De, (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
+  const unsigned grid = (unsigned)(N * L);
+  if (dtype == AMPCONV_BF16)
+    table_grad_kernel<<<grid, 64, 0, (hipStream_t)stream>>>((const __bf16 *)dout, idx, De, dtable);
+  else
+    table_grad_kernel<<<grid, 64, 0, (hipStream_t)stream>>>((const float *)dout, idx, De, dtable);
   return ampconv_launch_status();
 }
 
 extern "C" int ampconv_feat_table_grad(const float *dout, const int32_t *idx, int64_t N, int L, int De, int F,
                                        float *dtable, void *stream) {
-  if (!dout || !idx || !dtable || N <= 0 || L <= 0 || De <= 0 || F <= 0 || N * L > INT32_MAX)
-    return AMPCONV_E_BADARG;
-  hipError_t e = hipMemsetAsync(dtable, 0, sizeof(float) * (size_t)F * De, (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  table_grad_kernel<<<(unsigned)(N * L), 64, 0, (hipStream_t)stream>>>(dout, idx, De, dtable);
-  return ampconv_launch_status();
+  return ampconv_feat_table_grad_from(dout, idx, N, L, De, F, dtable, AMPCONV_F32, stream);
 }

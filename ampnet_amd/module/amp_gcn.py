@@ -16,6 +16,11 @@ The per-node Python
 sampling loop of :132-149 is replaced by csrc/featurizer.hip; the random stream is this library's (seeded);
 `forward(data, feature_indices=...)` takes the indices of another stream (tests: the reference's own).
 Pinned against the reference's class by tests/golden/model_*.npz (oracle/make_golden_ampgcn.py).
+
+`storage_dtype=torch.bfloat16` (not in the reference): the two AMPConv layers, their parameters and every [N, L*D] tensor
+between the featuriser and the pooling are stored in bf16 -- the library's fastest edge and projection kernels --; the
+embedding table, the LayerNorm sites and final_linear_out stay fp32, and so does every accumulation.  Train it with
+ampnet_amd.FusedAdam, which steps the bf16 parameters on fp32 masters.
 """
 import torch
 import torch.nn as nn
@@ -30,22 +35,31 @@ from ..stats import tensor_stats
 from ..graph import _stream
 
 
+_STORAGE = {torch.float32: _lib.AMPCONV_F32, torch.bfloat16: _lib.AMPCONV_BF16}
+
+
 class _BuildTokens(torch.autograd.Function):
     """tokens[n, l] = concat(table[idx[n, l]], zscore(x)[n, idx[n, l]]); gradient to `table` only
-    (x is data; the reference's x_.requires_grad_(True) leaf is never used by an optimiser)."""
+    (x is data; the reference's x_.requires_grad_(True) leaf is never used by an optimiser).  `dtype` is the storage of
+    the tokens (float32 or bfloat16: the fp32 value rounded to nearest even) and of the gradient that comes back for them;
+    the table and its gradient are fp32 either way."""
 
     @staticmethod
-    def forward(ctx, table, x, mean, inv_std, idx):
+    def forward(ctx, table, x, mean, inv_std, idx, dtype=torch.float32):
         lib = _lib.load()
+        if table.dtype != torch.float32:
+            raise ValueError(f'the feature embedding table is {table.dtype}: it stays float32 (the featuriser kernels read '
+                             f'fp32; AMPGCN(storage_dtype=torch.bfloat16) casts the conv layers only)')
         N, Fdim = x.shape
         L, De = idx.size(1), table.size(1)
-        out = torch.empty(N, L, De + 1, dtype=torch.float32, device=x.device)
+        out = torch.empty(N, L, De + 1, dtype=dtype, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.check(lib.ampconv_feat_build(x.data_ptr(), mean.data_ptr(), inv_std.data_ptr(), idx.data_ptr(),
-                                              table.data_ptr(), N, Fdim, L, De, out.data_ptr(), _stream()),
-                       'ampconv_feat_build')
+            _lib.check(lib.ampconv_feat_build_as(x.data_ptr(), mean.data_ptr(), inv_std.data_ptr(), idx.data_ptr(),
+                                                 table.data_ptr(), N, Fdim, L, De, out.data_ptr(), _STORAGE[dtype],
+                                                 _stream()), 'ampconv_feat_build_as')
         ctx.save_for_backward(idx)
         ctx.dims = (N, L, De, table.size(0))
+        ctx.storage = dtype
         return out
 
     @staticmethod
@@ -54,18 +68,21 @@ class _BuildTokens(torch.autograd.Function):
         (idx,) = ctx.saved_tensors
         N, L, De, Fdim = ctx.dims
         dtable = torch.empty(Fdim, De, dtype=torch.float32, device=dout.device)
-        dout = dout.contiguous()
+        dout = dout.to(ctx.storage).contiguous()
         with torch.cuda.device(dout.device):
-            _lib.check(lib.ampconv_feat_table_grad(dout.data_ptr(), idx.data_ptr(), N, L, De, Fdim,
-                                                   dtable.data_ptr(), _stream()), 'ampconv_feat_table_grad')
-        return dtable, None, None, None, None
+            _lib.check(lib.ampconv_feat_table_grad_from(dout.data_ptr(), idx.data_ptr(), N, L, De, Fdim, dtable.data_ptr(),
+                                                        _STORAGE[ctx.storage], _stream()), 'ampconv_feat_table_grad_from')
+        return dtable, None, None, None, None, None
 
 
 class FeatureTokens(nn.Module):
     """z-score + present-feature sampling + embedding concat (amp_gcn.py:120-183, downsampling branch)."""
 
-    def __init__(self, num_node_features, feat_emb_dim, num_sampled_vectors, seed=0):
+    def __init__(self, num_node_features, feat_emb_dim, num_sampled_vectors, seed=0, token_dtype=torch.float32):
         super().__init__()
+        if token_dtype not in _STORAGE:
+            raise ValueError(f'tokens are written as float32 or bfloat16, not {token_dtype}')
+        self.token_dtype = token_dtype
         self.feature_embedding_table = nn.Embedding(num_embeddings=num_node_features, embedding_dim=feat_emb_dim)
         self.num_sampled_vectors = num_sampled_vectors
         self._seed, self._calls = int(seed), 0
@@ -110,7 +127,7 @@ class FeatureTokens(nn.Module):
                              '(torch.cat / reshape of amp_gcn.py:174-181 raise otherwise)')
         idx = torch.arange(x.size(1), dtype=torch.int32, device=x.device).repeat(x.size(0), 1)
         mean, inv_std = self.zscore_stats(x)
-        tokens = _BuildTokens.apply(table.contiguous(), x, mean, inv_std, idx)
+        tokens = _BuildTokens.apply(table.contiguous(), x, mean, inv_std, idx, self.token_dtype)
         return tokens.view(x.size(0), -1), None
 
     def forward(self, x, idx=None):
@@ -125,7 +142,8 @@ class FeatureTokens(nn.Module):
                 raise ValueError('a node has no present (non-zero) feature to sample from '
                                  '(np.random.choice raises in the reference, amp_gcn.py:135)')
         mean, inv_std = self.zscore_stats(x)
-        tokens = _BuildTokens.apply(self.feature_embedding_table.weight, x, mean, inv_std, idx.contiguous())
+        tokens = _BuildTokens.apply(self.feature_embedding_table.weight, x, mean, inv_std, idx.contiguous(),
+                                    self.token_dtype)
         return tokens.view(x.size(0), -1), idx
 
 
@@ -133,8 +151,12 @@ class AMPGCN(nn.Module):
     def __init__(self, device="cuda", embedding_dim=100, num_heads=2, num_node_features=1433,
                  num_sampled_vectors=40, output_dim=7, softmax_out=True, feat_emb_dim=99, val_emb_dim=1,
                  downsample_feature_vectors=True, average_pooling_flag=True, dropout_rate=0.1,
-                 dropout_adj_rate=0.1, feature_repeats=5, seed=0, fused_glue=False, fused_head=False, layer_norm=False):
+                 dropout_adj_rate=0.1, feature_repeats=5, seed=0, fused_glue=False, fused_head=False, layer_norm=False,
+                 storage_dtype=torch.float32):
         super().__init__()
+        if storage_dtype not in _STORAGE:
+            raise ValueError(f'storage_dtype is torch.float32 or torch.bfloat16, got {storage_dtype}')
+        self.storage_dtype = storage_dtype
         assert embedding_dim == feat_emb_dim + val_emb_dim, \
             "Feature and value dimensions do not add up to total embedding dimension"
         if val_emb_dim != 1:
@@ -155,7 +177,7 @@ class AMPGCN(nn.Module):
         self.sampled_node_feat_indices = None
         self.conv1_embedding = self.conv2_embedding = None
         # same sub-module names as the reference => same state-dict keys
-        self._tokens = [FeatureTokens(num_node_features, feat_emb_dim, num_sampled_vectors, seed)]
+        self._tokens = [FeatureTokens(num_node_features, feat_emb_dim, num_sampled_vectors, seed, storage_dtype)]
         self.feature_embedding_table = self._tokens[0].feature_embedding_table
         if not average_pooling_flag:               # defined (and in the state dict) but never used by forward,
             self.cls_token = nn.Parameter(torch.zeros(1, 1, self.emb_dim))    # exactly as amp_gcn.py:55-57,268-271
@@ -167,6 +189,11 @@ class AMPGCN(nn.Module):
         self.final_linear_out = nn.Linear(in_features=embedding_dim, out_features=output_dim)
         self.drop3 = nn.Dropout(p=dropout_rate)
         self.act_out = nn.Sigmoid()
+        # storage_dtype=torch.bfloat16: the layers are built in fp32 (the reference's RNG consumption) and then cast, so the
+        # initial parameters are the rounded fp32 ones under the same keys; everything else stays fp32.
+        if storage_dtype != torch.float32:
+            self.conv1.to(storage_dtype)
+            self.conv2.to(storage_dtype)
         # fused_glue: drop1, ReLU -> drop2 and ReLU -> drop3 -> pooling as one HIP pass each (ampnet_amd/glue.py), masks from
         # this library's seeded stream instead of torch's.  Kept in a list like _tokens: the sites have no parameters and
         # the state dict stays the reference's.  Off (the default): the PyTorch ops below, torch's random stream.
@@ -189,10 +216,22 @@ class AMPGCN(nn.Module):
         if self.fused_head and output_dim > MAX_CLASSES:
             raise ValueError(f'fused_head supports output_dim <= {MAX_CLASSES}, got {output_dim}')
 
+    def _check_storage(self):
+        """model.float() / model.to(torch.bfloat16) cast every parameter; the kernels behind the table, the norm sites and
+        the head read fp32 and the layers read storage_dtype."""
+        convs = {p.dtype for conv in (self.conv1, self.conv2) for p in conv.parameters()}
+        rest = {p.dtype for n, p in self.named_parameters() if not n.startswith(('conv1.', 'conv2.'))}
+        if convs != {self.storage_dtype} or rest != {torch.float32}:
+            raise ValueError(f'AMPGCN(storage_dtype={self.storage_dtype}) needs conv1 / conv2 in {self.storage_dtype} and every '
+                             f'other parameter in torch.float32, found {sorted(map(str, convs))} and {sorted(map(str, rest))}: '
+                             f'a cast of the whole model (model.float(), model.to(torch.bfloat16)) is not a storage mode -- '
+                             f'construct the model with the storage_dtype you want')
+
     def _pooled(self, data, feature_indices=None):
         """forward() up to the token pooling: [N, embedding_dim], the input of final_linear_out.
         (_activation_sites below walks the same layer sequence in eval mode and keeps every intermediate tensor: a change
         of the sequence here has to be made there as well; tests/test_gpu_diagnostics.py holds the two together.)"""
+        self._check_storage()
         x, edge_index = data.x.to(self.device), data.edge_index.to(self.device)
         if self.training and self.dropout_adj_rate > 0:                       # dropout_adj (amp_gcn.py:241)
             keep = torch.rand(edge_index.size(1), device=edge_index.device) >= self.dropout_adj_rate
@@ -242,7 +281,7 @@ class AMPGCN(nn.Module):
         if self.fused_head:
             return classifier_head(x, self.final_linear_out.weight, self.final_linear_out.bias,
                                    'log_softmax' if self.softmax_out else 'sigmoid')
-        x = self.final_linear_out(x)
+        x = self.final_linear_out(x.float())                                  # (bf16 storage: the pooled rows are bf16)
         return F.log_softmax(x, dim=1) if self.softmax_out else self.act_out(x)
 
     def attention_heatmap(self, layer='conv1', src_features=None, dst_features=None, *, num_features=None,
@@ -300,6 +339,7 @@ class AMPGCN(nn.Module):
         return tensor_stats(sites, bins=bins, median=True)
 
     def _activation_sites(self, data, feature_indices):
+        self._check_storage()
         x, edge_index = data.x.to(self.device), data.edge_index.to(self.device)
         if self.downsampling_vectors:
             idx = feature_indices
@@ -336,7 +376,7 @@ class AMPGCN(nn.Module):
             a = a.reshape(a.shape[0], a.shape[1] // D, D)
             pooled = a.mean(dim=1) if self.average_pooling_flag else a[:, 0]
         sites['Average Pooling' if self.average_pooling_flag else 'Class Token'] = pooled.contiguous()
-        sites['Linear Out'] = F.linear(pooled, self.final_linear_out.weight, self.final_linear_out.bias)
+        sites['Linear Out'] = F.linear(pooled.float(), self.final_linear_out.weight, self.final_linear_out.bias)
         return {k: v.contiguous() for k, v in sites.items()}
 
     @staticmethod

@@ -13,7 +13,13 @@ copied to the device, nothing is read back, the step counts stay host integers.
     loss.backward(); opt.step(set_to_none=True); sched.step()
     # data parallel: reducer.allreduce(unpack=False); opt.step(grads=reducer.views, grad_scale=1 / world, set_to_none=True)
 
-float32 contiguous parameters on the GPU only; no amsgrad, maximize or capturable; no CPU or eager fallback.
+Contiguous float32 or bfloat16 parameters on the GPU only; no amsgrad, maximize or capturable; no CPU or eager fallback.
+
+bf16 STORAGE.  A bfloat16 parameter (AMPGCN(storage_dtype=torch.bfloat16)) is stepped on an fp32 master copy,
+state[p]['master']: an update of lr = 1e-3 on a bf16 weight near 1 is below half a bf16 ulp and torch.optim.Adam on the
+bf16 tensor loses every one of them.  The moments are fp32, gradients may be fp32 or bf16, the arithmetic is the fp32
+step's on the master, and the parameter is rewritten as the rounded master in the same launch.  An all-fp32 set runs the
+fp32 entry points exactly as before.
 """
 import ctypes
 import math
@@ -26,17 +32,22 @@ from .graph import _stream
 CHUNK = _lib.ADAM_CHUNK                  # elements per workgroup (AMPCONV_ADAM_CHUNK)
 MAX_TENSORS = _lib.ADAM_MAX_TENSORS      # descriptors per launch (AMPCONV_ADAM_MAX_TENSORS)
 
-_SUPPORTED = ('FusedAdam supports contiguous float32 parameters on the GPU with dense float32 gradients of the same shape '
-              'and device, without amsgrad, maximize or capturable (ampnet_amd has no CPU or eager fallback)')
+_SUPPORTED = ('FusedAdam supports contiguous float32 or bfloat16 parameters on the GPU with dense float32 or bfloat16 gradients '
+              'of the same shape and device, without amsgrad, maximize or capturable (ampnet_amd has no CPU or eager fallback)')
+_DTYPES = {torch.float32: _lib.AMPCONV_F32, torch.bfloat16: _lib.AMPCONV_BF16}
+_FP32_STATE = ('exp_avg', 'exp_avg_sq', 'master')
 _REFUSED = ('amsgrad', 'maximize', 'capturable')
 _ENTRY = ctypes.sizeof(_lib.AdamTensor)
+_MIXED_ENTRY = ctypes.sizeof(_lib.AdamMixedTensor)
 
 
 class FusedAdam(torch.optim.Optimizer):
     """Drop-in for torch.optim.Adam (decoupled=False: L2 weight decay) and torch.optim.AdamW (decoupled=True) on the
     formulas of include/ampconv.h, "optimizer step".  A real Optimizer: param_groups with a python-float lr (torch's LR
     schedulers drive it unchanged), per-parameter state `step` (a host integer), `exp_avg`, `exp_avg_sq` created at the
-    first step in which the parameter has a gradient; state dicts go to and come from torch.optim.Adam / AdamW.
+    first step in which the parameter has a gradient; state dicts go to and come from torch.optim.Adam / AdamW.  A bfloat16
+    parameter also has `master`, its fp32 value (from p.float() at that first step, or when a loaded state lacks it); the
+    moments and the master stay fp32 through state_dict() / load_state_dict().
 
     max_grad_norm: clip the global gradient norm over ALL groups to it, as torch.nn.utils.clip_grad_norm_ before the step;
     the norm and the coefficient never leave the device.  track_grad_norm: take the norm without clipping.  With either,
@@ -84,9 +95,56 @@ class FusedAdam(torch.optim.Optimizer):
         for st in self.state.values():
             if 'step' in st:
                 st['step'] = int(st['step'].item()) if isinstance(st['step'], torch.Tensor) else int(st['step'])
-            for k in ('exp_avg', 'exp_avg_sq'):
+            for k in _FP32_STATE:
                 if k in st:
                     st[k] = st[k].to(torch.float32).contiguous()
+
+    def load_state_dict(self, state_dict):
+        """torch casts loaded state to the parameter's dtype, which would round the moments and the master of a bfloat16
+        parameter to bf16: they are taken from `state_dict` again, in fp32."""
+        super().load_state_dict(state_dict)
+        ids = [i for group in state_dict['param_groups'] for i in group['params']]
+        params = [p for group in self.param_groups for p in group['params']]
+        for i, p in zip(ids, params):
+            saved = state_dict['state'].get(i)
+            if saved is None or p.dtype == torch.float32:
+                continue
+            for k in _FP32_STATE:
+                if k in saved:
+                    self.state[p][k] = saved[k].detach().to(device=p.device, dtype=torch.float32, copy=True).contiguous()
+
+    def full_precision_state_dict(self, model):
+        """model.state_dict() with every bfloat16 parameter of this optimizer replaced by its fp32 master (p.float() where it
+        has none yet): the keys are the model's own -- for AMPGCN the reference's --, so the checkpoint loads into an fp32
+        model.  Copies; nothing is shared with the model or the state."""
+        named = dict(model.named_parameters())
+        out = {}
+        for k, t in model.state_dict().items():
+            p = named.get(k)
+            if p is not None and p.dtype == torch.bfloat16:
+                master = self.state.get(p, {}).get('master')
+                out[k] = (master if master is not None else p.detach().float()).clone()
+            else:
+                out[k] = t.detach().clone()
+        return out
+
+    @torch.no_grad()
+    def load_full_precision_state_dict(self, model, state_dict):
+        """The way back: every entry is copied into the model (a bfloat16 parameter receives the rounded value) and the
+        exact fp32 value becomes the master of a bfloat16 parameter.  The keys have to be the model's."""
+        own = model.state_dict()
+        if set(own) != set(state_dict):
+            raise KeyError(f'state dict keys differ from the model\'s: missing {sorted(set(own) - set(state_dict))}, '
+                           f'unexpected {sorted(set(state_dict) - set(own))}')
+        named = dict(model.named_parameters())
+        for k, t in own.items():
+            src = state_dict[k].detach().to(t.device)
+            if src.shape != t.shape:
+                raise ValueError(f'{k}: shape {tuple(src.shape)} for a {tuple(t.shape)} tensor')
+            t.copy_(src)
+            p = named.get(k)
+            if p is not None and p.dtype == torch.bfloat16:
+                self.state[p]['master'] = src.to(torch.float32, copy=True).contiguous()
 
     @staticmethod
     def _check_group(group):
@@ -98,15 +156,15 @@ class FusedAdam(torch.optim.Optimizer):
 
     @staticmethod
     def _check_pair(p, g):
+        if p.dtype not in _DTYPES:
+            raise ValueError(f'a parameter is {p.dtype}; {_SUPPORTED}')
         if not p.is_cuda:
             raise ValueError(f'a parameter is on {p.device}, not on the GPU; {_SUPPORTED}')
-        if p.dtype != torch.float32:
-            raise ValueError(f'a parameter is {p.dtype}; {_SUPPORTED}')
         if not p.is_contiguous():
             raise ValueError(f'a parameter of shape {tuple(p.shape)} is not contiguous; {_SUPPORTED}')
         if not isinstance(g, torch.Tensor) or g.is_sparse or g.layout != torch.strided:
             raise ValueError(f'a gradient is {"sparse" if isinstance(g, torch.Tensor) else type(g).__name__}; {_SUPPORTED}')
-        if g.dtype != torch.float32 or g.device != p.device or g.shape != p.shape:
+        if g.dtype not in _DTYPES or g.device != p.device or g.shape != p.shape:
             raise ValueError(f'a gradient is {g.dtype} {tuple(g.shape)} on {g.device} for a {tuple(p.shape)} parameter on '
                              f'{p.device}; {_SUPPORTED}')
 
@@ -146,43 +204,55 @@ class FusedAdam(torch.optim.Optimizer):
                     keep.append(g)
                 pairs.append((p, g))
             work.append(pairs)
+        # an all-fp32 step runs the fp32 entry points, as it always has; a bfloat16 parameter or gradient the mixed ones
+        mixed = any(p.dtype != torch.float32 or g.dtype != torch.float32 for pairs in work for p, g in pairs)
         entries, spans = [], []
         for group, pairs in zip(self.param_groups, work):
             lr, (beta1, beta2) = float(group['lr']), group['betas']
             spans.append((len(entries), len(pairs)))
             for p, g in pairs:
                 st = self.state[p]
-                if not st:
+                if 'step' not in st:
                     st['step'] = 0
-                    st['exp_avg'] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                    st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                    st['exp_avg'] = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
+                    st['exp_avg_sq'] = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
+                if p.dtype == torch.bfloat16 and 'master' not in st:
+                    st['master'] = p.detach().to(torch.float32, memory_format=torch.contiguous_format)
                 st['step'] += 1
                 t = st['step']
-                entries.append((p.data_ptr(), g.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr(), p.numel(),
-                                lr / (1.0 - beta1 ** t), 1.0 / math.sqrt(1.0 - beta2 ** t)))
+                row = (p.data_ptr(), g.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr())
+                tail = (p.numel(), lr / (1.0 - beta1 ** t), 1.0 / math.sqrt(1.0 - beta2 ** t))
+                if mixed:
+                    master = st['master'].data_ptr() if p.dtype == torch.bfloat16 and p.numel() else None
+                    entries.append(row + (master,) + tail + (_DTYPES[p.dtype], _DTYPES[g.dtype]))
+                else:
+                    entries.append(row + tail)
         want_norm = self.max_grad_norm is not None or self.track_grad_norm
         if entries or (want_norm and params and params[0].is_cuda):
             device = device if device is not None else params[0].device
             lib = _lib.load()
-            table = (_lib.AdamTensor * len(entries))(*entries)
+            kind, size = (_lib.AdamMixedTensor, _MIXED_ENTRY) if mixed else (_lib.AdamTensor, _ENTRY)
+            prefix = 'ampconv_adam_mixed_' if mixed else 'ampconv_adam_'
+            table = (kind * len(entries))(*entries)
             norm = None
             with torch.cuda.device(device):
                 stream = _stream()
                 if want_norm:
                     norm = torch.empty((), dtype=torch.float32, device=device)
-                    ws = torch.empty(lib.ampconv_adam_workspace_bytes(table, len(entries)), dtype=torch.uint8, device=device)
-                    _lib.check(lib.ampconv_adam_grad_norm(table, len(entries), grad_scale, norm.data_ptr(), ws.data_ptr(),
-                                                          ws.numel(), stream), 'ampconv_adam_grad_norm')
+                    ws = torch.empty(getattr(lib, prefix + 'workspace_bytes')(table, len(entries)), dtype=torch.uint8,
+                                     device=device)
+                    _lib.check(getattr(lib, prefix + 'grad_norm')(table, len(entries), grad_scale, norm.data_ptr(),
+                                                                  ws.data_ptr(), ws.numel(), stream), prefix + 'grad_norm')
                     self.grad_norm = norm
                 clip = norm.data_ptr() if self.max_grad_norm is not None else None
                 for group, (first, count) in zip(self.param_groups, spans):
                     if count == 0:
                         continue
-                    rows = ctypes.cast(ctypes.byref(table, first * _ENTRY), ctypes.POINTER(_lib.AdamTensor))
-                    _lib.check(lib.ampconv_adam_step(rows, count, float(group['lr']), group['betas'][0], group['betas'][1],
-                                                     group['eps'], group['weight_decay'],
-                                                     int(bool(group['decoupled_weight_decay'])), grad_scale, clip,
-                                                     self.max_grad_norm or 0.0, stream), 'ampconv_adam_step')
+                    rows = ctypes.cast(ctypes.byref(table, first * size), ctypes.POINTER(kind))
+                    _lib.check(getattr(lib, prefix + 'step')(rows, count, float(group['lr']), group['betas'][0],
+                                                             group['betas'][1], group['eps'], group['weight_decay'],
+                                                             int(bool(group['decoupled_weight_decay'])), grad_scale, clip,
+                                                             self.max_grad_norm or 0.0, stream), prefix + 'step')
         if set_to_none:
             for p in params:
                 p.grad = None

@@ -5,7 +5,7 @@ AMPGCN(D=128, H=4, L=20) + GraphSAINT random-walk batches + Adam + cosine warm r
 node_norm-weighted NLL.  Everything between the data and the loss runs on the GPU.
 
     python examples/train_graphsaint.py [--epochs 3] [--dropout 0.1 --fused-glue] [--fused-head] [--layer-norm]
-                                        [--fused-adam [--clip M] [--track-grad-norm]] [--diagnostics K [--diag-dir DIR]]
+                                        [--fused-adam [--clip M] [--track-grad-norm] [--bf16]] [--diagnostics K [--diag-dir DIR]]
                                         [--model gcn [--gcn-input {embedded,zscore,raw}] [--hidden 16]]
 
 --model gcn trains the baseline behind the reference's `TRAIN_AMPCONV = False` (:27,58-75): the 2-layer GCN of
@@ -100,6 +100,9 @@ def main(argv=None):
                     help='with --fused-adam: clip the global gradient norm to M on the device (FusedAdam(max_grad_norm=M))')
     ap.add_argument('--track-grad-norm', action='store_true',
                     help="with --fused-adam: print the last batch's gradient norm with the epoch's read-back")
+    ap.add_argument('--bf16', action='store_true',
+                    help='AMPGCN(storage_dtype=torch.bfloat16): the two AMPConv layers and the activations between them in '
+                         'bf16 storage, table / norms / head in fp32; needs --fused-adam, which keeps fp32 master weights')
     ap.add_argument('--diagnostics', type=int, default=0, metavar='K',
                     help="every K-th batch queues the reference's gradient and activation diagnostics (experiments/"
                          'cora_benchmark_graphsaint.py:111-114) as device-side statistics (AMPGCN.gradient_stats / '
@@ -111,6 +114,12 @@ def main(argv=None):
         ap.error('--diag-dir needs --diagnostics K')
     if (args.clip is not None or args.track_grad_norm) and not args.fused_adam:
         ap.error('--clip and --track-grad-norm need --fused-adam')
+    if args.bf16 and not args.fused_adam:
+        ap.error('--bf16 needs --fused-adam: torch.optim.Adam would step the bf16 parameters themselves, and an update of '
+                 'lr * O(1) on a weight near 1 is below half a bf16 ulp -- it is lost at every step; FusedAdam steps fp32 '
+                 'master copies and writes the rounded result')
+    if args.bf16 and args.model == 'gcn':
+        ap.error('--bf16 belongs to --model ampgcn (GCN is float32 only)')
     if args.model == 'gcn' and (args.layer_norm or args.diagnostics > 0 or args.class_defaults):
         ap.error('--layer-norm, --diagnostics and --class-defaults belong to --model ampgcn')
     device = torch.device('cuda:0')
@@ -126,8 +135,9 @@ def main(argv=None):
         model = AMPGCN(device=device, embedding_dim=D, num_heads=H, num_node_features=1433, num_sampled_vectors=L,
                        output_dim=7, softmax_out=True, feat_emb_dim=D - 1, val_emb_dim=1, dropout_rate=args.dropout,
                        dropout_adj_rate=0.0, fused_glue=args.fused_glue, fused_head=args.fused_head,
-                       layer_norm=args.layer_norm).to(device)
-        what = 'sampler + 2 AMPConv layers fwd+bwd + Adam'
+                       layer_norm=args.layer_norm,
+                       storage_dtype=torch.bfloat16 if args.bf16 else torch.float32).to(device)
+        what = 'sampler + 2 AMPConv layers fwd+bwd + Adam' + (', bf16 storage' if args.bf16 else '')
     loader = GraphSAINTRandomWalkSampler(data, batch_size=8, walk_length=150, num_steps=args.steps,
                                          sample_coverage=20, seed=1)
     if args.fused_adam:
@@ -191,6 +201,7 @@ def main(argv=None):
         out = model(data)                                                   # full-graph eval (:159-163)
         acc = float((out.argmax(1) == data.y)[data.test_mask].float().mean())
     print(f'full-graph test accuracy {acc:.3f}')
+    main.last_run = (model, opt)                                            # for callers that look at the trained state
     return history, acc
 
 

@@ -516,6 +516,14 @@ int ampconv_feat_build(const float *x, const float *mean, const float *inv_std, 
                        const float *table, int64_t N, int F, int L, int De, float *out, void *stream);
 int ampconv_feat_table_grad(const float *dout, const int32_t *idx, int64_t N, int L, int De, int F,
                             float *dtable, void *stream);
+/* The same two with the token storage given (`dtype`: AMPCONV_F32 or AMPCONV_BF16, else AMPCONV_E_DTYPE; pure additions,
+ * the ABI number stays 111).  feat_build_as: every element of `out` is the round-to-nearest-even `dtype` value of what
+ * ampconv_feat_build writes, for any De >= 0.  feat_table_grad_from: `dout` [N, L, De + 1] is read in `dtype`, widened and
+ * accumulated in fp32 into the fp32 dtable, with the same float atomics.  */
+int ampconv_feat_build_as(const float *x, const float *mean, const float *inv_std, const int32_t *idx,
+                          const float *table, int64_t N, int F, int L, int De, void *out, int dtype, void *stream);
+int ampconv_feat_table_grad_from(const void *dout, const int32_t *idx, int64_t N, int L, int De, int F, float *dtable,
+                                 int dtype, void *stream);
 
 /* ---- glue around the layers: activation, dropout, token pooling (csrc/glue.hip, ABI 109) ------------------------
  * Reference src/ampnet/module/amp_gcn.py:239-276: drop1 -> conv1 -> ReLU -> drop2 -> conv2 -> ReLU -> drop3 -> token
@@ -707,6 +715,43 @@ int ampconv_adam_grad_norm(const ampconv_adam_tensor_t *t, int n, float grad_sca
 int ampconv_adam_step(const ampconv_adam_tensor_t *t, int n, float lr, double beta1, double beta2, float eps,
                       float weight_decay, int decoupled, float grad_scale, const float *norm, float max_grad_norm,
                       void *stream);
+
+/* ---- mixed-precision optimizer step (csrc/optim.hip; pure additions, the ABI number stays 111) -----------------------
+ * The step above for parameters stored in bf16 and for gradients of either dtype; descriptors of both dtypes mix freely in
+ * one call.  The formulas of "optimizer step" are evaluated in fp32 on the fp32 VALUE of the parameter: `master` for a
+ * bf16 p, p itself for an fp32 p.  The gradient is widened to fp32 first (exact); weight decay, decoupled or L2, acts on
+ * the fp32 value.  m, v and master are updated in place; a bf16 p is then written as the round-to-nearest-even bf16 of the
+ * new master (torch's .to(torch.bfloat16)).  A bf16 update of lr = 1e-3 on a parameter near 1 is below half a bf16 ulp and
+ * would be lost every step; the master keeps it.
+ * MAPPING.  The chunks, the grid and a lane's elements 4 j .. 4 j + 3 are those of the fp32 step whatever the dtypes; a
+ * piece is four elements of its own stream (16 bytes fp32, 8 bytes bf16).  A tensor whose pointers are ALL aligned to
+ * their own piece is walked in pieces with an element-wise tail, any other tensor element by element.
+ * DETERMINISM.  Every rounding of the step is pinned in the source (csrc/optim.hip, "ROUNDING"): a bf16 gradient gives the
+ * norm and the outputs of the same call on its widened fp32 copy; alignment changes no bit; all-fp32 descriptors give the
+ * bits of ampconv_adam_grad_norm always and the bits of ampconv_adam_step on every tensor whose p, g, m and v are 16-byte
+ * aligned.  (ampconv_adam_step forms the denominator with one rounding in its 16-byte pieces and with two in its
+ * element-wise path; the mixed step takes the former for every whole group of four elements and the latter for the up to
+ * three elements behind the last one, by position, so it cannot follow ampconv_adam_step on a tensor that is not 16-byte
+ * aligned without letting alignment change bits.)
+ * ERRORS: everything the fp32 entry points refuse, a dtype code other than AMPCONV_F32 / AMPCONV_BF16, a NULL master with
+ * a bf16 p (numel > 0), a non-NULL master with an fp32 p: AMPCONV_E_BADARG -- nothing is launched.  */
+typedef struct {
+  void *p;            /* parameter, storage p_dtype */
+  const void *g;      /* gradient, storage g_dtype (independent of p_dtype) */
+  float *m;           /* exp_avg: always fp32 */
+  float *v;           /* exp_avg_sq: always fp32 */
+  float *master;      /* fp32 copy of p: required when p_dtype == AMPCONV_BF16, NULL when AMPCONV_F32 */
+  int64_t numel;
+  float step_size;    /* lr / (1 - beta1^t) */
+  float inv_bc2_sqrt; /* 1 / sqrt(1 - beta2^t) */
+  int32_t p_dtype, g_dtype;
+} ampconv_adam_mixed_tensor_t; /* 64 bytes */
+size_t ampconv_adam_mixed_workspace_bytes(const ampconv_adam_mixed_tensor_t *t, int n);
+int ampconv_adam_mixed_grad_norm(const ampconv_adam_mixed_tensor_t *t, int n, float grad_scale, float *norm,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+int ampconv_adam_mixed_step(const ampconv_adam_mixed_tensor_t *t, int n, float lr, double beta1, double beta2, float eps,
+                            float weight_decay, int decoupled, float grad_scale, const float *norm, float max_grad_norm,
+                            void *stream);
 
 /* ---- tensor statistics (csrc/stats.hip; pure additions, the ABI number stays 111) ----------------------------------------
  * Reference: src/ampnet/module/amp_gcn.py:278-405 copies every weight gradient and five [N, L*D] activation tensors to the

@@ -1,0 +1,365 @@
+"""bf16-storage AMPGCN on the GPU: the featuriser's bf16 kernels (csrc/featurizer.hip), AMPGCN(storage_dtype=torch.bfloat16)
+as exact plumbing of pieces that are each tested on their own, its accuracy against the fp64 oracle, training through
+examples/train_graphsaint.py --bf16 and a two-process data-parallel step under FusedAdam.
+
+Inputs: x [96, 64] sparse with at least one present feature per node, E = 400 edges with repeated destinations and sources.
+Shapes: L = 8, D = 32, H = 2 (dh = 16: the bf16 matrix-core kernels) and L = 24, D = 40, H = 2 (dh = 20: the
+workgroup-per-unit kernels), each as fused_glue + fused_head and as layer_norm (whose head is the unfused one: the pooled
+rows are cast to fp32 in front of final_linear_out).  Eval mode, feature indices passed in."""
+import functools
+import importlib.util
+import os
+import types
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import norm_reference as nr
+from conftest import ROOT, assert_close_scaled
+
+pytestmark = pytest.mark.gpu
+
+DEV = 'cuda:0'
+BF16 = torch.bfloat16
+N, FEATS, E, CLASSES = 96, 64, 400, 5
+SHAPES = {'dh16': (8, 32, 2), 'dh20': (24, 40, 2)}                        # L, D, H
+FLAGS = {'fused': dict(fused_glue=True, fused_head=True), 'norm': dict(layer_norm=True)}
+CASES = [(s, f) for s in SHAPES for f in FLAGS]
+
+
+@functools.lru_cache(maxsize=None)
+def _graph():
+    """(x, edge_index) on the host, drawn once."""
+    g = torch.Generator().manual_seed(11)
+    x = (torch.rand(N, FEATS, generator=g) < 0.15).float() * (1.0 + torch.rand(N, FEATS, generator=g))
+    x[torch.arange(N), torch.randint(0, FEATS, (N,), generator=g)] = 1.0     # at least one present feature per node
+    ei = torch.randint(0, N, (2, E), generator=g)
+    ei[1, :12] = 3                                                           # repeated destinations ...
+    ei[0, 12:24] = 7                                                         # ... and sources
+    return x, ei
+
+
+@functools.lru_cache(maxsize=None)
+def _indices(L):
+    """Present features per node, with replacement, from numpy's stream (as the reference samples)."""
+    x, _ = _graph()
+    rng = np.random.default_rng(L)
+    return torch.from_numpy(np.stack([rng.choice(np.flatnonzero(row), L) for row in x.numpy()]).astype(np.int32))
+
+
+def _data():
+    x, ei = _graph()
+    return types.SimpleNamespace(x=x.to(DEV), edge_index=ei.to(DEV))
+
+
+def _model(shape, flags, storage=BF16):
+    from ampnet_amd import AMPGCN
+    L, D, H = SHAPES[shape]
+    torch.manual_seed(21)
+    model = AMPGCN(device=DEV, embedding_dim=D, num_heads=H, num_node_features=FEATS, num_sampled_vectors=L,
+                   output_dim=CLASSES, feat_emb_dim=D - 1, dropout_rate=0.1, dropout_adj_rate=0.1, storage_dtype=storage,
+                   **FLAGS[flags]).to(DEV)
+    with torch.no_grad():                                                    # biases and norm parameters off their trivial init
+        g = torch.Generator().manual_seed(22)
+        for name, p in model.named_parameters():
+            if name.endswith('bias') or name.startswith('norm'):
+                p.add_((torch.randn(p.shape, generator=g) * 0.1).to(DEV, p.dtype))
+    return model.eval()
+
+
+def _bits(a, b):
+    """The same dtype, shape and bit patterns (torch.equal alone takes -0.0 for 0.0 and no NaN for itself)."""
+    ints = lambda t: t.detach().contiguous().view({4: torch.int32, 2: torch.int16}[t.element_size()])
+    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(ints(a), ints(b))
+
+
+# ---- the featuriser's kernels
+
+@pytest.mark.parametrize('width', [1, 3, 32, 100])
+def test_bf16_tokens_are_the_rounded_fp32_tokens(width):
+    """ampconv_feat_build_as(BF16) against ampconv_feat_build, through the C boundary (De = 0 has no table to give a
+    module): every element, odd row widths included, is the fp32 value rounded to nearest even; a node without a present
+    feature (index -1) gets zero rows in both."""
+    from ampnet_amd import _lib
+    lib = _lib.load()
+    De, L = width - 1, 8
+    x = _graph()[0].to(DEV)
+    idx = _indices(L).clone()
+    idx[5] = -1
+    idx = idx.to(DEV)
+    g = torch.Generator().manual_seed(31)
+    table = torch.randn(FEATS, max(De, 1), generator=g).to(DEV)[:, :De].contiguous() if De else torch.zeros(1, device=DEV)
+    mean = torch.randn(FEATS, generator=g).to(DEV)
+    inv_std = (torch.rand(FEATS, generator=g) + 0.5).to(DEV)
+    out32 = torch.full((N, L, width), float('nan'), device=DEV)
+    again32 = torch.full((N, L, width), float('nan'), device=DEV)
+    out16 = torch.full((N, L, width), float('nan'), device=DEV, dtype=BF16)
+    head = (x.data_ptr(), mean.data_ptr(), inv_std.data_ptr(), idx.data_ptr(), table.data_ptr(), N, FEATS, L, De)
+    assert lib.ampconv_feat_build(*head, out32.data_ptr(), None) == 0
+    assert lib.ampconv_feat_build_as(*head, again32.data_ptr(), _lib.AMPCONV_F32, None) == 0
+    assert lib.ampconv_feat_build_as(*head, out16.data_ptr(), _lib.AMPCONV_BF16, None) == 0
+    assert lib.ampconv_feat_build_as(*head, out16.data_ptr(), 2, None) == -2        # AMPCONV_E_DTYPE
+    torch.cuda.synchronize()
+    assert not torch.isnan(out32).any() and (out32[5] == 0).all() and out32[6].abs().sum() > 0
+    assert _bits(again32, out32)
+    assert _bits(out16, out32.to(BF16))
+
+
+@pytest.mark.parametrize('shape', list(SHAPES))
+def test_table_gradient_from_a_bf16_token_gradient(shape):
+    """The float-atomic accumulation of tests/test_gpu_featurizer.py on a widened bf16 gradient, at that file's bar
+    (rtol = atol = 1e-5): N L / F = 12 and 36 unit-size terms per table element."""
+    from ampnet_amd.module.amp_gcn import FeatureTokens
+    L, D, _ = SHAPES[shape]
+    torch.manual_seed(41)
+    ft = FeatureTokens(FEATS, D - 1, L, token_dtype=BF16).to(DEV)
+    idx = _indices(L).to(DEV)
+    tokens, _ = ft(_graph()[0].to(DEV), idx)
+    assert tokens.dtype == BF16 and tokens.shape == (N, L * D)
+    dout = torch.randn(N, L, D, generator=torch.Generator().manual_seed(42)).to(DEV, BF16)
+    tokens.backward(dout.view(N, L * D))
+    got = ft.feature_embedding_table.weight.grad
+    assert got.dtype == torch.float32
+    want = torch.zeros(FEATS, D - 1, dtype=torch.float64, device=DEV)
+    want.index_add_(0, idx.reshape(-1).long(), dout[..., :D - 1].double().reshape(-1, D - 1))
+    torch.testing.assert_close(got.double(), want, rtol=1e-5, atol=1e-5)
+    # the fp32 entry point still takes the fp32 gradient
+    ft32 = FeatureTokens(FEATS, D - 1, L).to(DEV)
+    tok32, _ = ft32(_graph()[0].to(DEV), idx)
+    assert tok32.dtype == torch.float32
+    tok32.backward(dout.float().view(N, L * D))
+    torch.testing.assert_close(ft32.feature_embedding_table.weight.grad.double(), want, rtol=1e-5, atol=1e-5)
+
+
+def test_full_width_tokens_in_bf16():
+    """The full-width branch (every feature column a token, the table tiled feature_repeats times): bf16 tokens are the
+    rounded fp32 ones, the gradient of the untiled table stays fp32 and is the fp32 branch's (384 unit-size terms per
+    element, float atomics in both: the bar of test_table_gradient_from_a_bf16_token_gradient)."""
+    from ampnet_amd.module.amp_gcn import FeatureTokens
+    torch.manual_seed(43)
+    ft32 = FeatureTokens(16, 7, FEATS).to(DEV)
+    ft16 = FeatureTokens(16, 7, FEATS, token_dtype=BF16).to(DEV)
+    ft16.load_state_dict(ft32.state_dict())
+    x = _graph()[0].to(DEV)
+    t32, idx32 = ft32.forward_all(x, 4)
+    t16, idx16 = ft16.forward_all(x, 4)
+    assert idx32 is None and idx16 is None and t16.shape == (N, FEATS * 8) and _bits(t16, t32.to(BF16))
+    dout = torch.randn(N, FEATS * 8, generator=torch.Generator().manual_seed(44)).to(DEV, BF16)
+    t16.backward(dout)
+    t32.backward(dout.float())
+    g16, g32 = ft16.feature_embedding_table.weight.grad, ft32.feature_embedding_table.weight.grad
+    assert g16.dtype == torch.float32 and g16.shape == (16, 7)
+    torch.testing.assert_close(g16, g32, rtol=1e-5, atol=1e-5)
+
+
+def test_a_bf16_embedding_table_is_refused():
+    from ampnet_amd.module.amp_gcn import FeatureTokens
+    ft = FeatureTokens(FEATS, 7, 8).to(DEV).to(BF16)
+    with pytest.raises(ValueError, match='stays float32'):
+        ft(_graph()[0].to(DEV), _indices(8).to(DEV))
+
+
+# ---- the model
+
+def _composition(model, data, idx):
+    """What AMPGCN(storage_dtype=bfloat16) computes in eval mode, from public pieces that take no storage_dtype: fp32
+    tokens cast to bf16, a bf16 AMPConv per layer with the model's parameters, the glue / norm sites, the head."""
+    from ampnet_amd import AMPConv, act_dropout, act_dropout_pool, classifier_head, norm_act_dropout, norm_act_dropout_pool
+    from ampnet_amd.module.amp_gcn import FeatureTokens
+    L, D, H = model.num_sampled_vectors, model.emb_dim, model.conv1.num_heads
+    ft = FeatureTokens(FEATS, D - 1, L)
+    ft.feature_embedding_table = model.feature_embedding_table
+    tokens, _ = ft(data.x, idx)
+    assert tokens.dtype == torch.float32
+    convs = []
+    for own in (model.conv1, model.conv2):
+        conv = AMPConv(D, H).to(DEV).to(BF16)
+        conv.load_state_dict(own.state_dict())
+        convs.append(conv.eval())
+    h = act_dropout(tokens.to(BF16), 0.0, 'identity', False)
+    e1 = convs[0](h, data.edge_index)
+    if model.layer_norm:
+        a1 = norm_act_dropout(e1, D, model.norm1.weight, model.norm1.bias, model.norm1.eps, 0.0, 'relu', False)
+        e2 = convs[1](a1, data.edge_index)
+        pooled = norm_act_dropout_pool(e2, D, model.norm2.weight, model.norm2.bias, model.norm2.eps, 0.0, 'relu', 'mean', False)
+    else:
+        a1 = act_dropout(e1, 0.0, 'relu', False)
+        e2 = convs[1](a1, data.edge_index)
+        pooled = act_dropout_pool(e2, D, 0.0, 'relu', 'mean', False)
+    W, b = model.final_linear_out.weight, model.final_linear_out.bias
+    out = classifier_head(pooled, W, b, 'log_softmax') if model.fused_head else F.log_softmax(F.linear(pooled.float(), W, b), dim=1)
+    return out, e1, e2, convs
+
+
+@pytest.mark.parametrize('shape,flags', CASES)
+def test_the_model_is_exact_plumbing(shape, flags):
+    model, data = _model(shape, flags), _data()
+    idx = _indices(SHAPES[shape][0]).to(DEV)
+    with torch.no_grad():
+        got = model(data, feature_indices=idx)
+        e1, e2 = model.conv1_embedding, model.conv2_embedding
+        want, w1, w2, _ = _composition(model, data, idx)
+    assert got.dtype == torch.float32 and got.shape == (N, CLASSES) and e1.dtype == e2.dtype == BF16
+    assert _bits(e1, w1) and _bits(e2, w2) and _bits(got, want)
+    assert torch.isfinite(got).all() and float(got.exp().sum(dim=1).sub(1).abs().max()) < 1e-5
+    assert all(p.dtype == BF16 for p in list(model.conv1.parameters()) + list(model.conv2.parameters()))
+    assert model.feature_embedding_table.weight.dtype == model.final_linear_out.weight.dtype == torch.float32
+
+
+def _f64(t):
+    return t.detach().float().cpu().numpy().astype(np.float64)
+
+
+def _oracle(model, dlogp):
+    """log-probabilities and parameter gradients of sum(logp * dlogp) in fp64 on the model's parameters as they are stored
+    (bf16 ones widened): oracle.ampgcn_numpy.AMPGCNOracle, and for layer_norm its two layers around the LayerNorm model of
+    tests/norm_reference.py (the oracle class has no norm sites)."""
+    from oracle.ampgcn_numpy import AMPGCNOracle
+    x, ei = _graph()
+    L, D, H = model.num_sampled_vectors, model.emb_dim, model.conv1.num_heads
+    idx = _indices(L).numpy().astype(np.int64)
+    state = {k: _f64(v) for k, v in model.state_dict().items()}
+    o = AMPGCNOracle(state, H)
+    if not model.layer_norm:
+        return o.forward(x.numpy(), ei.numpy(), idx), o.backward(dlogp)
+    n1 = (state['norm1.weight'], state['norm1.bias'], model.norm1.eps, 'relu')
+    n2 = (state['norm2.weight'], state['norm2.bias'], model.norm2.eps, 'relu')
+    t0 = o.tokens(x.numpy(), idx)
+    e1, _ = o.convs[0].forward(t0, ei.numpy(), need_weights=False)
+    a1, _ = nr.norm_fwd(e1, D, *n1, 0, 0.0)
+    e2, _ = o.convs[1].forward(a1, ei.numpy(), need_weights=False)
+    pooled, _ = nr.norm_pool_fwd(e2, L, D, *n2, 'mean', 0, 0.0)
+    z = pooled @ o.Wf.T + o.bf
+    z = z - z.max(axis=1, keepdims=True)
+    logp = z - np.log(np.exp(z).sum(axis=1, keepdims=True))
+    dz = dlogp - np.exp(logp) * dlogp.sum(axis=1, keepdims=True)
+    grads = {'final_linear_out.weight': dz.T @ pooled, 'final_linear_out.bias': dz.sum(axis=0)}
+    d, grads['norm2.weight'], grads['norm2.bias'] = nr.norm_pool_bwd(e2, dz @ o.Wf, L, D, *n2, 'mean', 0, 0.0)
+    for name, conv, pre, site in (('conv2', o.convs[1], e1, n1), ('conv1', o.convs[0], None, None)):
+        dx, dWin, dbin, dWo, dbo = conv.backward(d)
+        for key, val in (('in_proj_weight', dWin), ('in_proj_bias', dbin), ('out_proj.weight', dWo), ('out_proj.bias', dbo)):
+            grads[f'{name}.multi_head_attention.{key}'] = val
+        if pre is not None:
+            d, grads['norm1.weight'], grads['norm1.bias'] = nr.norm_bwd(pre, dx, D, *site, 0, 0.0)
+    dtab = np.zeros((FEATS, D - 1))
+    np.add.at(dtab, idx.reshape(-1), dx.reshape(N, L, D)[..., :D - 1].reshape(-1, D - 1))
+    grads['feature_embedding_table.weight'] = dtab
+    return logp, grads
+
+
+# The project's bf16 bar (tests/test_gpu_parity.py::test_bf16_storage) is rtol = atol = 2e-2 of the tensor's scale, set for ONE
+# layer.  Measured on the MI355X for the composition of existing pieces that the model is bit for bit
+# (profiles/bf16_model.md has every tensor): the log-probabilities use 0.4 % .. 4.7 % of that bar in all four cases and every
+# gradient of the L = 24 cases fits it (at most 67 %), but the L = 8 cases exceed it in a few isolated elements -- largest
+# scaled error 6.10e-2 (fused: conv2 out_proj.bias.grad, one of 32 elements) and 3.21e-2 (norm: the same tensor).  Cause: the
+# ReLU between and behind the layers.  A bf16 layer places a few hundred of the 24576 second-layer activations within its own
+# error of zero; where the sign differs from fp64 the token's whole share of the pooled gradient, 1 / L of it, appears or
+# vanishes in the gradients of conv2's out-projection and of everything in front of it.  At L = 8 one such flip moves
+# out_proj.bias.grad by up to 0.08 on a scale of 3.7; at L = 24 by a third of that.  That is a property of the existing bf16
+# path under a discontinuous activation, not of the model class, so those two cases are held to TWICE the recorded value
+# (the factor covers accumulation-order differences), the other two to the project's bar.
+BAR = {('dh16', 'fused'): 2 * 6.10e-2, ('dh16', 'norm'): 2 * 3.21e-2, ('dh20', 'fused'): 2e-2, ('dh20', 'norm'): 2e-2}
+
+
+@pytest.mark.parametrize('shape,flags', CASES)
+def test_accuracy_against_the_fp64_oracle(shape, flags):
+    """Two chained bf16 layers (activations rounded to bf16 between them) against fp64 on the same stored parameters.  The
+    model adds no error of its own to the composition of its pieces (test_the_model_is_exact_plumbing), so what is
+    measured is the existing bf16 path, twice in a row; the bars and where they come from: BAR above."""
+    model, data = _model(shape, flags), _data()
+    idx = _indices(SHAPES[shape][0]).to(DEV)
+    dlogp = torch.randn(N, CLASSES, generator=torch.Generator().manual_seed(51))
+    out = model(data, feature_indices=idx)
+    (out * dlogp.to(DEV)).sum().backward()
+    logp, grads = _oracle(model, dlogp.numpy().astype(np.float64))
+    named = dict(model.named_parameters())
+    assert set(grads) == set(named)
+    failures = []
+    for name, got, want in [('log-probabilities', out, logp)] + [(f'{k}.grad', named[k].grad, grads[k]) for k in named]:
+        try:
+            assert_close_scaled(_f64(got), want, f'{shape} {flags} {name}', atol=BAR[shape, flags], rtol=BAR[shape, flags],
+                                scaled=True)
+        except AssertionError as e:                                            # every tensor's figure is printed before any fails
+            failures.append(str(e))
+    assert not failures, '\n'.join(failures)
+    assert all(named[k].grad.dtype == named[k].dtype for k in named)
+
+
+def _example():
+    spec = importlib.util.spec_from_file_location('train_graphsaint_bf16', os.path.join(ROOT, 'examples', 'train_graphsaint.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_the_example_trains_in_bf16_storage():
+    """The two assertions of the fp32 harness test (tests/test_gpu_featurizer.py): the loss goes down and the model ends
+    above 0.4 on held-out nodes (chance: 1/7); then every bf16 parameter is its master, rounded."""
+    mod = _example()
+    history, acc = mod.main(['--epochs', '4', '--steps', '15', '--bf16', '--fused-adam', '--fused-glue', '--fused-head'])
+    print(f'bf16 storage: loss {history[0][0]:.4f} -> {history[-1][0]:.4f}, held-out accuracy {acc:.3f}')
+    assert history[-1][0] < history[0][0]
+    assert acc > 0.4
+    model, opt = mod.main.last_run
+    seen = 0
+    for name, p in model.named_parameters():
+        if name.startswith(('conv1.', 'conv2.')):
+            assert p.dtype == BF16 and _bits(p.detach(), opt.state[p]['master'].to(BF16)), name
+            assert not torch.equal(p.detach().float(), opt.state[p]['master']), name       # the master holds more bits
+            seen += 1
+        else:
+            assert p.dtype == torch.float32 and 'master' not in opt.state[p], name
+    assert seen == 8
+
+
+def test_the_example_refuses_bf16_without_fused_adam(capsys):
+    mod = _example()
+    with pytest.raises(SystemExit):
+        mod.main(['--bf16'])
+    assert 'needs --fused-adam' in capsys.readouterr().err
+
+
+def _dp_worker(rank, world, port, out_dir):
+    import torch.distributed as dist
+    os.environ['MASTER_ADDR'] = '127.0.0.1'
+    os.environ['MASTER_PORT'] = str(port)
+    dist.init_process_group('gloo', rank=rank, world_size=world)                 # both ranks share cuda:0 here
+    from ampnet_amd import FusedAdam
+    from ampnet_amd.distributed import GradientAllReducer
+    model = _model('dh16', 'fused').train()                                      # the same seed: equal parameters on both ranks
+    params = list(model.parameters())
+    reducer = GradientAllReducer(params)
+    opt = FusedAdam(params, lr=1e-3, weight_decay=1e-4, max_grad_norm=1.0)
+    x, ei = _graph()
+    g = torch.Generator().manual_seed(70 + rank)                                 # one batch per rank
+    idx = _indices(8).to(DEV)
+    for _ in range(3):
+        keep = torch.rand(E, generator=g) < 0.7
+        data = types.SimpleNamespace(x=x.to(DEV), edge_index=ei[:, keep].to(DEV))
+        y = torch.randint(0, CLASSES, (N,), generator=g).to(DEV)
+        model.nll_loss(data, y=y, feature_indices=idx).backward()
+        flat = reducer.allreduce(unpack=False)
+        views = reducer.views
+        assert flat.dtype == torch.float32 and all(v.dtype == torch.float32 for v in views)
+        assert all(p.grad.dtype == p.dtype for p in params)
+        opt.step(grads=views, grad_scale=1.0 / world, set_to_none=True)
+    torch.save({'params': [p.detach().cpu() for p in params],
+                'masters': [opt.state[p]['master'].cpu() for p in params if p.dtype == BF16],
+                'norm': opt.grad_norm.cpu()}, os.path.join(out_dir, f'r{rank}.pt'))
+    dist.destroy_process_group()
+
+
+def test_data_parallel_step_on_a_bf16_model(tmp_path):
+    import socket
+    import torch.multiprocessing as mp
+    s = socket.socket(); s.bind(('127.0.0.1', 0)); port = s.getsockname()[1]; s.close()
+    mp.spawn(_dp_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    r = [torch.load(os.path.join(tmp_path, f'r{i}.pt')) for i in range(2)]
+    assert len(r[0]['masters']) == 8 and _bits(r[0]['norm'], r[1]['norm'])
+    for key in ('params', 'masters'):
+        assert all(_bits(a, b) for a, b in zip(r[0][key], r[1][key])), key
+    start = [p.detach().cpu() for p in _model('dh16', 'fused').parameters()]
+    assert any(not torch.equal(a, b) for a, b in zip(start, r[0]['params']))     # it did train
+    assert all(_bits(p, m.to(BF16)) for p, m in zip([p for p in r[0]['params'] if p.dtype == BF16], r[0]['masters']))

@@ -1,6 +1,6 @@
 """Developer benchmark: one optimizer step over AMPGCN's actual parameter set, ampnet_amd.FusedAdam beside torch.optim.Adam.
 
-    python tools/bench_optim.py [--steps S] [--no-train] [--only VARIANT]
+    python tools/bench_optim.py [--steps S] [--no-train] [--only VARIANT] [--bf16]
 
 Parameter sets: AMPGCN at 128 / 4 / 20 (experiments/cora_benchmark_graphsaint.py) and at the class defaults 100 / 2 / 40,
 each with and without layer_norm; every parameter gets a random gradient once.  Variants, all with lr=0.1,
@@ -11,7 +11,10 @@ weight_decay=1e-4 and the zeroing of the gradients that belongs to a training st
     torch fused      torch.optim.Adam(fused=True): zero_grad() + step()
 Per set and variant: the median over S steps (default 300, after 20 warm-up steps, variants alternating) of the HIP-event
 time of one step, and the kernel launches of one step counted by torch.profiler.  --only runs one variant for S steps
-and nothing else (for a kernel trace of exactly that variant).  Unless --no-train: the per-batch time that
+and nothing else (for a kernel trace of exactly that variant).  --bf16: the class-default set only, as
+AMPGCN(storage_dtype=torch.bfloat16) holds it -- conv parameters and their gradients in bf16, the rest fp32 --, FusedAdam's
+mixed-precision step (fp32 masters) with and without clipping; the torch variants are left out (torch.optim.Adam on bf16
+parameters is a different, lossy computation).  Unless --no-train: the per-batch time that
 examples/train_graphsaint.py --fused-head prints for its last epoch, with and without --fused-adam, each in a child
 process.  Prints a markdown table and one JSON line.  Needs a GPU (no fallback).
 """
@@ -41,11 +44,12 @@ def opt(name, default, kind=int):
     return kind(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
 
 
-def make_variant(name, shapes, dev):
+def make_variant(name, shapes, dev, dtypes=None):
     """(prepare, step): prepare() attaches the gradients (not timed), step() is what a training step runs."""
     g = torch.Generator().manual_seed(0)
-    params = [torch.nn.Parameter(torch.randn(s, generator=g).to(dev)) for s in shapes]
-    grads = [(torch.randn(s, generator=g) * 0.01).to(dev) for s in shapes]
+    dtypes = dtypes or [torch.float32] * len(shapes)
+    params = [torch.nn.Parameter(torch.randn(s, generator=g).to(dev, dt)) for s, dt in zip(shapes, dtypes)]
+    grads = [(torch.randn(s, generator=g) * 0.01).to(dev, dt) for s, dt in zip(shapes, dtypes)]
 
     def prepare():
         for p, gr in zip(params, grads):
@@ -89,22 +93,23 @@ def launches(prepare, step):
         return None
 
 
-def parameter_shapes(cfg, layer_norm):
-    model = AMPGCN(device='cpu', dropout_rate=0.0, dropout_adj_rate=0.0, layer_norm=layer_norm, **cfg)
-    return [tuple(p.shape) for p in model.parameters()]
+def parameter_shapes(cfg, layer_norm, storage_dtype=torch.float32):
+    model = AMPGCN(device='cpu', dropout_rate=0.0, dropout_adj_rate=0.0, layer_norm=layer_norm, storage_dtype=storage_dtype,
+                   **cfg)
+    return [tuple(p.shape) for p in model.parameters()], [p.dtype for p in model.parameters()]
 
 
-def bench(label, cfg, layer_norm, steps, dev):
-    shapes = parameter_shapes(cfg, layer_norm)
-    routes = {v: make_variant(v, shapes, dev) for v in VARIANTS}
-    ms = {v: [] for v in VARIANTS}
+def bench(label, cfg, layer_norm, steps, dev, variants=VARIANTS, storage_dtype=torch.float32):
+    shapes, dtypes = parameter_shapes(cfg, layer_norm, storage_dtype)
+    routes = {v: make_variant(v, shapes, dev, dtypes) for v in variants}
+    ms = {v: [] for v in variants}
     for r in range(steps + 20):                                     # alternating; the first 20 rounds are warm-up
-        for v in VARIANTS:
+        for v in variants:
             t = timed(*routes[v])
             if r >= 20:
                 ms[v].append(t)
     row = {'set': label, 'tensors': len(shapes), 'elements': sum(int(torch.Size(s).numel()) for s in shapes)}
-    for v in VARIANTS:
+    for v in variants:
         row[v] = {'ms_median': statistics.median(ms[v]), 'ms_min': min(ms[v]), 'ms_max': max(ms[v]),
                   'launches': launches(*routes[v])}
     return row
@@ -126,12 +131,31 @@ def main():
     only = opt('--only', None, str)
     if only is not None:                                            # one variant, nothing else: for a kernel trace
         label, cfg, ln = SETS[2]
-        prepare, step = make_variant(only, parameter_shapes(cfg, ln), dev)
+        shapes, dtypes = parameter_shapes(cfg, ln, torch.bfloat16 if '--bf16' in sys.argv else torch.float32)
+        prepare, step = make_variant(only, shapes, dev, dtypes)
         for _ in range(steps):
             prepare()
             step()
         torch.cuda.synchronize()
         print(f'{only}: {steps} steps over the {label} set')
+        return
+    if '--bf16' in sys.argv:                                        # the class-default set, fp32 and bf16 storage side by side
+        label, cfg, ln = SETS[2]
+        variants = VARIANTS[:2]
+        rows = [bench(label + ' fp32', cfg, ln, steps, dev, variants),
+                bench(label + ' bf16 storage', cfg, ln, steps, dev, variants, torch.bfloat16)]
+        print(f'{torch.cuda.get_device_name(0)}, one optimizer step, median of {steps} steps in ms (min .. max) / kernel launches')
+        for row in rows:
+            for v in variants:
+                print(f'| {row["set"]} | {v} | {row[v]["ms_median"]:.4f} ({row[v]["ms_min"]:.4f} .. {row[v]["ms_max"]:.4f}) / '
+                      f'{row[v]["launches"] or "not measured"} |')
+        if '--no-train' not in sys.argv:
+            for extra in (['--fused-adam'], ['--fused-adam', '--bf16'], ['--fused-adam', '--class-defaults'],
+                          ['--fused-adam', '--class-defaults', '--bf16']):
+                ms, lines = train_ms(extra)
+                rows.append({'train': extra, 'ms_per_batch_last_epoch': ms, 'log': lines})
+                print(f'examples/train_graphsaint.py --epochs 4 --fused-head {" ".join(extra)}: {ms:.2f} ms per sampled batch')
+        print(json.dumps({'steps': steps, 'device': torch.cuda.get_device_name(0), 'rows': rows}))
         return
     result = {'steps': steps, 'device': torch.cuda.get_device_name(0), 'rows': [bench(*s, steps, dev) for s in SETS]}
     print(f'{result["device"]}, one optimizer step, median of {steps} steps in ms (min .. max) / kernel launches')
