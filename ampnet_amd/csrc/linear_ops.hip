@@ -73,13 +73,19 @@ int check(int64_t N, int L, int D, int H) {
   return AMPCONV_OK;
 }
 
+// a view none of whose strides is 0: a zero stride would fold nodes, tokens or heads onto each other (in an output:
+// several wavefronts storing to the same elements)
+bool lview_ok(const ampconv_view_t &v) {
+  return view_ok(v) && v.node_stride != 0 && v.row_stride != 0 && v.head_stride != 0;
+}
+
 }  // namespace
 
 extern "C" int ampconv_linear_outer(ampconv_view_t A, ampconv_view_t B, int64_t N, int L, int D, int H, float scale,
                                     float *M, void *stream) {
   if (int rc = check(N, L, D, H)) return rc;
   if (N == 0) return AMPCONV_OK;
-  if (!view_ok(A) || !view_ok(B) || !M) return AMPCONV_E_BADARG;
+  if (!lview_ok(A) || !lview_ok(B) || !M) return AMPCONV_E_BADARG;
   const int dh = D / H;
   LArgs a{A, B, M, N * H, L, dh, H, scale, 0};
   const size_t lds = (size_t)2 * L * (dh | 1) * sizeof(float);
@@ -92,7 +98,7 @@ extern "C" int ampconv_linear_apply(ampconv_view_t A, const float *M, int transp
                                     float scale, ampconv_view_t Out, void *stream) {
   if (int rc = check(N, L, D, H)) return rc;
   if (N == 0) return AMPCONV_OK;
-  if (!view_ok(A) || !view_ok(Out) || !M) return AMPCONV_E_BADARG;
+  if (!lview_ok(A) || !lview_ok(Out) || !M) return AMPCONV_E_BADARG;
   const int dh = D / H;
   LArgs a{A, Out, const_cast<float *>(M), N * H, L, dh, H, scale, transpose};
   const size_t lds = (size_t)(L + dh) * (dh | 1) * sizeof(float);

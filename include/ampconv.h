@@ -336,7 +336,15 @@ int ampconv_attn_heatmap_shift(void);   /* AMPCONV_HEATMAP_SHIFT of the loaded b
  * (out-projection bias must not leak into nodes nobody sends to).
  * masked_colsum: out[f] = sum over rows with a non-empty segment of dY[n, f],
  * folded over the L tokens: out has D fp32 entries (out_proj.bias gradient).
- * `dtype` of Y / dY: AMPCONV_F32 or AMPCONV_BF16.  */
+ * `dtype` of Y / dY: AMPCONV_F32 or AMPCONV_BF16.
+ * mask_rows stores +0 over the rows it zeroes, whatever they held (NaN and infinity included), and reads and writes
+ * no other row.  It has two paths with the same result: 16-byte stores where Y is 16-byte aligned AND a row is a
+ * multiple of 16 bytes (F * sizeof % 16 == 0), element stores for any other base address or row length -- no alignment
+ * is asked of the caller.  `rowptr` may be the `ptr` array of ampconv_active_nodes: the rows of the nodes a list
+ * leaves out are zeroed.
+ * masked_colsum does not read the rows it leaves out (they may hold NaN); N == 0 gives D zeros; the result is bitwise
+ * reproducible.  `out` needs room for D results followed by a scratch area of 1024 * D floats.
+ * segment_mean: a message row no edge names is not read; E == 0 (every segment empty) gives zeros, msg may be NULL.  */
 int ampconv_segment_mean(const float *msg, const int32_t *rowptr,
                          const int32_t *eperm, int64_t N, int64_t F, float *out,
                          void *stream);
@@ -355,7 +363,14 @@ int ampconv_gather_segment_sum(const float *rows, const int32_t *ptr, const int3
  * [L, dh] tile per (node, head) on either side, M = [N, H, dh, dh] fp32 row-major:
  *   linear_outer: M[n,h] = scale * A[n,:,h]^T B[n,:,h]      (K^T V; Q^T dObar for the backward)
  *   linear_apply: Out[n,:,h] = scale * A[n,:,h] M[n,h]      (transpose != 0: ... M[n,h]^T)
- *                 (Q Mbar; dObar Mbar^T, V dM^T, K dM for the backward)  */
+ *                 (Q Mbar; dObar Mbar^T, V dM^T, K dM for the backward)
+ * Any dh, odd ones included (only the Python layer asks for an even head width); fp32 only.  One wavefront per
+ * (node, head) holds both operands of a unit in LDS, rows padded to dh | 1 floats, and a call that would need more than
+ * 64 KiB of it is refused: AMPCONV_E_BADARG, nothing launched or written, where
+ *   linear_outer: 2 L (dh | 1) * 4 > 65536   (dh = 64: L <= 126 is served, 127 is not)
+ *   linear_apply: (L + dh) (dh | 1) * 4 > 65536   (dh = 64: L <= 188; dh = 128 at no L).
+ * Also refused with AMPCONV_E_BADARG: a NULL M or view pointer, D % H != 0, and a view with a zero node, row or head
+ * stride (it would fold units onto each other).  N == 0 returns AMPCONV_OK and touches nothing.  */
 int ampconv_linear_outer(ampconv_view_t A, ampconv_view_t B, int64_t N, int L, int D, int H,
                          float scale, float *M, void *stream);
 int ampconv_linear_apply(ampconv_view_t A, const float *M, int transpose, int64_t N, int L,

@@ -119,6 +119,28 @@ def place(logical, layout, dtype, role, device='cuda:0'):
     return Placed(backing, view, index)
 
 
+def place_flat(logical, dtype, skew=0, device='cuda:0'):
+    """`place` for the calls that take a plain pointer: logical, an array of any shape, -> a contiguous INPUT buffer inside
+    a larger allocation with NaN in front of and behind it (float32 arrays are placed bit for bit); that shape as a tuple
+    -> an OUTPUT buffer, the whole allocation full of the sentinel.  The buffer begins `skew` elements behind a 256-byte
+    boundary.  Returns a Placed whose `ptr` is the buffer's address (`view`: None)."""
+    is_output = isinstance(logical, tuple)
+    shape = logical if is_output else logical.shape
+    n = int(np.prod(shape, dtype=np.int64))
+    margin = 64 * (1 + skew // 64) + 64
+    total = margin + skew + n + 64
+    if is_output:
+        backing = torch.full((total,), _sentinel(dtype), dtype=_INT[dtype], device=device).view(dtype)
+    else:
+        backing = torch.full((total,), float('nan'), dtype=dtype, device=device)
+        vals = torch.from_numpy(np.ascontiguousarray(logical))
+        backing[margin + skew:margin + skew + n] = vals.to(dtype).to(device).reshape(-1)
+    assert backing.data_ptr() % 64 == 0
+    p = Placed(backing, None, (margin + skew + torch.arange(n, device=device)).reshape(shape))
+    p.ptr = backing.data_ptr() + (margin + skew) * backing.element_size()
+    return p
+
+
 def read(backing, index):
     """The logical array (float64 numpy) behind a gather index."""
     return backing[index.reshape(-1)].reshape(index.shape).double().cpu().numpy()
