@@ -135,7 +135,17 @@ class FeatureTokens(nn.Module):
             raise ValueError('FeatureTokens needs float32 node features on the GPU (no CPU fallback)')
         x = x.contiguous()
         if idx is not None:
-            idx = torch.as_tensor(idx, device=x.device).to(torch.int32)
+            idx = torch.as_tensor(idx, device=x.device)
+            # given indices go straight into table[f] and x[n, f] on the device: refuse what would read out of bounds
+            # (one read-back, on this replay path only)
+            if idx.dim() != 2 or idx.size(0) != x.size(0) or idx.numel() == 0 or idx.is_floating_point():
+                raise ValueError(f'feature indices must be integers [{x.size(0)}, num_sampled_vectors], got '
+                                 f'{idx.dtype} {tuple(idx.shape)}')
+            lo, hi = int(idx.min()), int(idx.max())
+            width = min(x.size(1), self.feature_embedding_table.num_embeddings)
+            if lo < 0 or hi >= width:
+                raise ValueError(f'feature indices outside [0, {width}): min {lo}, max {hi}')
+            idx = idx.to(torch.int32)
         if idx is None:
             idx, empty = self.sample(x)
             if int(empty.item()):

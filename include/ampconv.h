@@ -489,7 +489,19 @@ int ampconv_absmax_stats(const void *X, int64_t ld, int64_t M, int K, float *out
  *                 so that n_sub and e_sub come back in ONE read)
  *   add_counts  : count[idx[i]] += 1 (occurrence statistics of nodes / edges)
  *   norms       : edge_norm = clamp(node_count[src] / edge_count, 0, 1e4) (NaN -> 0.1),
- *                 node_norm = num_samples / max(node_count, 0.1 if 0) / N               */
+ *                 node_norm = num_samples / max(node_count, 0.1 if 0) / N
+ *
+ * THE WALK STREAM (a contract, like THE MASK below: tests rebuild it on the host, tests/pipeline_reference.py).  With
+ *   draw(seed, a, b) = splitmix64(seed ^ splitmix64(a * 0x100000001B3 + b))      (uint64, wrapping; all 64 bits of seed)
+ * step t = 0, 1, ... of walk b leaves the current node u, of out-degree deg = cscptr[u + 1] - cscptr[u], for
+ *   crow[cscptr[u] + draw(seed, b, t) % deg]
+ * -- the (draw % deg)-th out-edge of u in CSC order, a duplicate edge counting once per copy -- and stays at u if
+ * deg == 0.  walk_length == 0 writes the starts alone.  A (seed, graph, starts) triple therefore always gives the same
+ * walks, on any device and in any launch shape.
+ * THE ORDER OF A SUB-GRAPH is part of the contract too: node_idx ascends; the edges of fill_edges stand at exact
+ * positions, grouped by source in ascending relabelled source k, within a source in CSC order (= ascending original
+ * edge id, the CSC being a stable sort), edge o of source k at off[k] + o.  Batches are reproducible element for
+ * element, not only as sets.  */
 int ampconv_saint_random_walk(const int32_t *cscptr, const int32_t *crow, const int64_t *start,
                               int64_t B, int walk_length, uint64_t seed, int64_t *walks, void *stream);
 size_t ampconv_saint_workspace_bytes(int64_t N);
@@ -522,7 +534,21 @@ int ampconv_saint_gather_rows(const void *src, int64_t src_stride_bytes, int64_t
  * (non-zero) features sampled per node with replacement (:132-135), token = concat(embedding row,
  * z-scored value) (:146-147).  x is [N, F] fp32, idx [N, L] int32 (-1 = node without any present
  * feature; `empty_flag` is raised), table [F, De], out [N, L, De + 1].  table_grad zeroes dtable and
- * accumulates the token gradients with float atomics.  */
+ * accumulates the token gradients with float atomics: rows no token names come back as exact zeros whatever dtable
+ * held; a token with idx -1 gives a zero row in feat_build and adds nothing in table_grad.
+ *
+ * THE SAMPLING STREAM (a contract, like THE MASK below: tests rebuild it on the host, tests/pipeline_reference.py).
+ * With draw(seed, a, b) = splitmix64(seed ^ splitmix64(a * 0x100000001B3 + b)) (uint64, wrapping; all 64 bits of seed)
+ * and count = the number of present columns of row n:
+ *   idx[n, l] = the (draw(seed, n, l) % count)-th present column of row n, counted from 0 in ascending column order.
+ * PRESENT means x[n, f] != 0 for a finite value: -0.0 is absent, denormals and negative values are present (the kernels
+ * run with fp32 denormals on).  The library is built with -fno-honor-nans, so a NaN feature has NO defined presence
+ * (today's build treats it as absent; numpy's `!=` would call it present): keep NaN out of x.
+ * ACCURACY OF THE STATISTICS: zscore_stats accumulates in double (population variance; sklearn's constant-feature rule
+ * var <= N eps var + (N mean eps)^2 gives scale 1) and returns mean and inv_std rounded to fp32, each within 1 ulp.  z is
+ * then assembled in fp32 as (x - mean) * inv_std, so the rounding of `mean` alone moves z by up to
+ * |mean| inv_std 2^-24: |z - z_fp64| <= 2^-24 (2 |mean| inv_std + 4 |z|).  For a column whose mean is large against its
+ * spread (1000 +- 0.01: |mean| inv_std = 1e5) that is 1e-2, not the 1e-7 of a centred column.  */
 int ampconv_feat_zscore_stats(const float *x, int64_t N, int64_t F, float *mean, float *inv_std,
                               void *stream);
 int ampconv_feat_sample_present(const float *x, int64_t N, int F, int L, uint64_t seed, int32_t *idx,

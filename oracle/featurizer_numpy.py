@@ -5,7 +5,9 @@ Follows /root/reference/src/ampnet/module/amp_gcn.py:
   :146-147  tokens = cat(embedding_table[idx], x_[node, idx][:, None])
   :152-153  reshape to [N, L * D]
 The sampling of :132-135 (np.random.choice over the present features, with replacement) is random:
-UNPINNED stream; `indices_are_present` states its defining property.
+UNPINNED stream (parity with the reference's numpy stream); `indices_are_present` states its defining property.
+The library's OWN stream is pinned: include/ampconv.h defines it ("THE SAMPLING STREAM"), tests/pipeline_reference.py
+rebuilds it on the host and tests/test_gpu_featurizer_kernels.py holds the kernel to it index for index.
 """
 import numpy as np
 from sklearn.preprocessing import StandardScaler

@@ -8,6 +8,9 @@ Follows /root/reference/visualization/visualize_graphsaint_subgraphs.py:
 Parity status of the random walk itself: UNPINNED -- it is torch_sparse's `random_walk` C++ op
 (third party, not installed, no fixture in the reference); walk_is_valid() checks the defining
 property instead (every step moves along an out-edge, or stays at a node without out-edges).
+The library's OWN walk stream and the order of a sub-graph's edges are pinned: include/ampconv.h defines them ("THE WALK
+STREAM", "THE ORDER OF A SUB-GRAPH"), tests/pipeline_reference.py rebuilds them on the host and
+tests/test_gpu_sampler_kernels.py holds the kernels to them element for element.
 """
 import numpy as np
 

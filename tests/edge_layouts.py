@@ -22,6 +22,12 @@ MIXED = {'Q': 'nhld', 'K': 'packed3', 'V': 'hnld', 'dO': 'pad16', 'out0': 'lnd',
 # quiet-NaN patterns no kernel produces (fp32: hip's NaN is 0x7FC00000; bf16: 0x7FC0)
 SENTINEL = {torch.float32: 0x7FC5A5A5, torch.bfloat16: 0x7FA5}
 _INT = {torch.float32: torch.int32, torch.bfloat16: torch.int16}
+# integer buffers (place_flat_int): outputs hold a pattern no index, count or offset of a test reaches; the margins of an
+# input hold -1, the one value that, taken for an index, count or pointer by a stray read, addresses nothing outside
+# the allocation's own margins
+SENTINEL.update({torch.int32: 0x5A5A5A5A, torch.int64: 0x5A5A5A5A5A5A5A5A})
+_INT.update({torch.int32: torch.int32, torch.int64: torch.int64})
+INT_POISON = -1
 
 
 def layout_strides(layout, N, L, H, dh, bf16=False):
@@ -82,6 +88,14 @@ class Placed:
         inside[(self.index if rows is None else self.index[rows]).reshape(-1)] = True
         return bool((self.bits()[~inside] == _sentinel(self.backing.dtype)).all())
 
+    def margins_hold(self, value):
+        """True iff every element outside the buffer still holds `value` (NaN: is NaN) -- for an INPUT the call also
+        writes (its margins hold NaN or INT_POISON, not the sentinel)."""
+        inside = torch.zeros(self.backing.numel(), dtype=torch.bool, device=self.backing.device)
+        inside[self.index.reshape(-1)] = True
+        out = self.backing[~inside]
+        return bool(torch.isnan(out).all() if value != value else (out == value).all())
+
     def unwritten(self, rows=None):
         """Number of elements of the view (of those nodes) that still hold the sentinel."""
         idx = (self.index if rows is None else self.index[rows]).reshape(-1)
@@ -90,7 +104,7 @@ class Placed:
 
 def _sentinel(dtype):
     s = SENTINEL[dtype]
-    return s if dtype == torch.float32 else s - (1 << 16) if s >= (1 << 15) else s
+    return s - (1 << 16) if dtype == torch.bfloat16 and s >= (1 << 15) else s
 
 
 def place(logical, layout, dtype, role, device='cuda:0'):
@@ -135,6 +149,25 @@ def place_flat(logical, dtype, skew=0, device='cuda:0'):
         backing = torch.full((total,), float('nan'), dtype=dtype, device=device)
         vals = torch.from_numpy(np.ascontiguousarray(logical))
         backing[margin + skew:margin + skew + n] = vals.to(dtype).to(device).reshape(-1)
+    assert backing.data_ptr() % 64 == 0
+    p = Placed(backing, None, (margin + skew + torch.arange(n, device=device)).reshape(shape))
+    p.ptr = backing.data_ptr() + (margin + skew) * backing.element_size()
+    return p
+
+
+def place_flat_int(logical, dtype, skew=0, device='cuda:0'):
+    """`place_flat` for int32 / int64 buffers: logical, an integer array of any shape, -> a contiguous INPUT buffer with
+    INT_POISON in front of and behind it; that shape as a tuple -> an OUTPUT buffer, the whole allocation full of the
+    integer sentinel.  `outside_intact` / `unwritten` work as for the float buffers; `margins_hold(INT_POISON)` checks an
+    input the call also writes."""
+    assert dtype in (torch.int32, torch.int64)
+    is_output = isinstance(logical, tuple)
+    shape = logical if is_output else np.shape(logical)
+    n = int(np.prod(shape, dtype=np.int64))
+    margin = 64 * (1 + skew // 64) + 64
+    backing = torch.full((margin + skew + n + 64,), SENTINEL[dtype] if is_output else INT_POISON, dtype=dtype, device=device)
+    if not is_output:
+        backing[margin + skew:margin + skew + n] = torch.from_numpy(np.ascontiguousarray(logical)).to(dtype).to(device).reshape(-1)
     assert backing.data_ptr() % 64 == 0
     p = Placed(backing, None, (margin + skew + torch.arange(n, device=device)).reshape(shape))
     p.ptr = backing.data_ptr() + (margin + skew) * backing.element_size()
