@@ -29,20 +29,11 @@
 // follows from the plane count alone (fragment reads, staging stores, LDS sizes) is written over it.
 // Reference arithmetic replaced: torch functional.py:6578-6594 per edge, the mean of amp_conv.py:11, and their autograd
 // backward.
-#include "mfma_tile.h"
+#include "plane16.h"
 
 namespace {
+using namespace plane16;      // conversions, plane_scale, split2, frag_sumsq, tr_half, TR_FRAG_FENCE / TR_WAR_GUARD
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-constexpr float kLog2eX = 1.4426950408889634f;
 constexpr int kRowB = 128;                 // one plane of a token row: 64 bf16 channels
 constexpr int kTileRowsB = 16 * kRowB;     // 16 token rows of one plane
 
@@ -57,16 +48,8 @@ struct XFrag {
   i32x4 p[P];
 };
 
-__device__ __forceinline__ int pk_bf(float a, float b) {      // v_cvt_pk_bf16_f32 (RNE)
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(int, __builtin_convertvector(v, bf16x2));
-}
 __device__ __forceinline__ float bfl(int u) { return __builtin_bit_cast(float, u << 16); }
 __device__ __forceinline__ float bfh(int u) { return __builtin_bit_cast(float, u & (int)0xFFFF0000u); }
-__device__ __forceinline__ int pk_h(float a, float b) {      // v_cvt_pk_f16_f32 (RNE)
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(int, __builtin_convertvector(v, f16x2));
-}
 
 // byte offset of 16-byte chunk `ch` (0..7) of token row j in a plane image
 __device__ __forceinline__ int xoff(int j, int ch) { return j * kRowB + ((ch ^ (((j >> 1) & 3) << 1)) << 4); }
@@ -302,9 +285,6 @@ __device__ __forceinline__ XFrag<P> rowfrag(const char *img, int aks, int t) {
   return f;
 }
 
-__device__ __forceinline__ i32x2 tr64(const char *p) {
-  return __builtin_bit_cast(i32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)p));
-}
 // token-product fragment (A operand, rows = channels 16 mc .. + 15) over the token tiles (2 pair, 2 pair + 1): k-slots
 // 0..3 = tokens 16 (2 pair) + 4 kg + 0..3, slots 4..7 = the same rows of the next tile (a last odd tile: its own values
 // again -- finite -- against zeros in the other operand).  `trb` = this lane's byte offset for channel tile mc.
@@ -315,9 +295,9 @@ __device__ __forceinline__ XFrag<P> colfrag(const char *img, int trb, int pair) 
   const bool two = 2 * pair + 1 < NT;
   i32x2 a[P], b[P];
 #pragma unroll
-  for (int pl = 0; pl < P; ++pl) a[pl] = tr64(p + pl * PB);
+  for (int pl = 0; pl < P; ++pl) a[pl] = tr_half(p + pl * PB);
 #pragma unroll
-  for (int pl = 0; pl < P; ++pl) b[pl] = two ? tr64(p + kTileRowsB + pl * PB) : a[pl];
+  for (int pl = 0; pl < P; ++pl) b[pl] = two ? tr_half(p + kTileRowsB + pl * PB) : a[pl];
   XFrag<P> f;
 #pragma unroll
   for (int pl = 0; pl < P; ++pl) f.p[pl] = i32x4{a[pl][0], a[pl][1], b[pl][0], b[pl][1]};
@@ -342,22 +322,6 @@ __device__ __forceinline__ typename Fmt::Frag cd_frag(const f32x4 (&T)[NT], int 
   for (int pl = 0; pl < P; ++pl) f.p[pl] = i32x4{w[0][pl], w[1][pl], w[2][pl], w[3][pl]};
   return f;
 }
-
-// every transposed fragment of a product group is in its registers before the group's first MFMA issues, and no
-// transposed read is scheduled in among the MFMAs (tests/test_abi.py scans the shipped ISA)
-#define X3_FRAG_FENCE()                                    \
-  do {                                                     \
-    __builtin_amdgcn_sched_barrier(0);                     \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     \
-    __builtin_amdgcn_sched_barrier(0);                     \
-  } while (0)
-// in front of a group of transposed reads that follows MFMAs (their fragment registers may be taken over)
-#define X3_PRE_READ()                          \
-  do {                                         \
-    __builtin_amdgcn_sched_barrier(0);         \
-    asm volatile("s_nop 7" ::: "memory");      \
-    __builtin_amdgcn_sched_barrier(0);         \
-  } while (0)
 
 // per-lane address parts of the fragment reads
 struct FragAddr {
@@ -418,7 +382,7 @@ __device__ __forceinline__ float store_xb(const ampconv_view_t &v, int64_t node,
 #pragma unroll
   for (int mc = 0; mc < MCT; ++mc) {
     const int c = 16 * mc + 4 * g;
-    const int p0 = pk_bf(T[mc][0] * scale, T[mc][1] * scale), p1 = pk_bf(T[mc][2] * scale, T[mc][3] * scale);
+    const int p0 = cvt_pk_bf16(T[mc][0] * scale, T[mc][1] * scale), p1 = cvt_pk_bf16(T[mc][2] * scale, T[mc][3] * scale);
     if constexpr (VEC == 4) {
       if (c < dh) *reinterpret_cast<i32x2 *>(row + c) = i32x2{p0, p1};
     } else {
@@ -556,12 +520,12 @@ struct FmtX3 : Fp32Storage {
 
   // (x0, x1) -> packed bf16 pairs of the three planes (the residuals are exact fp32 differences)
   static __device__ __forceinline__ void split(float x0, float x1, int (&w)[3]) {
-    w[0] = pk_bf(x0, x1);
+    w[0] = cvt_pk_bf16(x0, x1);
     float r0 = x0 - bfl(w[0]), r1 = x1 - bfh(w[0]);
-    w[1] = pk_bf(r0, r1);
+    w[1] = cvt_pk_bf16(r0, r1);
     r0 -= bfl(w[1]);
     r1 -= bfh(w[1]);
-    w[2] = pk_bf(r0, r1);
+    w[2] = cvt_pk_bf16(r0, r1);
   }
   // the six partial products of one fp32-grade product, smallest first (planes h, m, l = p[0], p[1], p[2])
   static __device__ __forceinline__ f32x4 mma(const Frag &a, const Frag &b, f32x4 c) {
@@ -599,37 +563,24 @@ struct FmtX3 : Fp32Storage {
 // of three and three partial products instead of six:
 //      a b ~ a_lo b_hi + a_hi b_lo + a_hi b_hi        (dropped: a_lo b_lo <= 2^-22 |a b|)
 // Half the matrix-pipe cycles, two thirds of the split's vector instructions and of the LDS traffic of the bf16 version.
-// The scale bookkeeping is that of edge_mfma_f16x2.hip: scores meet their scale inside the exponential, P is split as
+// Scale and split are those of plane16.h, the scale bookkeeping is that of edge_mfma_f16x2.hip: scores meet their scale
+// inside the exponential, P is split as
 // P 2^14, dS with one power of two per WAVE from what the wave can see (Cauchy-Schwarz: its own side's largest token-row
 // norm, sqrt(64) x the recorded maximum of the streamed tensor); dObar is divided by the in-degree here (own side: once
 // per unit, streamed side: in the staging pass), the statistics hand-off carries delta in the units of dP' = dO' V'^T.
-// 2^(14 - floor(log2 bound)), exponent field clamped (the function of proj_gemm.hip / edge_mfma_f16x2.hip)
-__device__ __forceinline__ float plane_scale_x(float bound) {
-  int e = (int)((__builtin_bit_cast(unsigned, bound) >> 23) & 0xFFu);
-  e = e < 15 ? 15 : (e > 254 ? 254 : e);
-  return __builtin_bit_cast(float, (unsigned)(268 - e) << 23);
-}
-__device__ __forceinline__ float frag_sumsq_h(const i32x4 &f) {
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const f16x2 v = __builtin_bit_cast(f16x2, f[k]);
-    s = __builtin_amdgcn_fdot2(v, v, s, false);
-  }
-  return s;
-}
+// (plane_scale, split2, frag_sumsq: plane16.h)
 // largest token-row norm^2 of the wave's own 16 tokens (hi planes of its two k-step fragments): wave-uniform
 template <int KS>
 __device__ __forceinline__ float own_max_norm2(const XFrag<2> (&f)[KS]) {
-  float q = frag_sumsq_h(f[0].p[0]);
-  if constexpr (KS == 2) q += frag_sumsq_h(f[1].p[0]);
+  float q = frag_sumsq(f[0].p[0]);
+  if constexpr (KS == 2) q += frag_sumsq(f[1].p[0]);
   const float t = groups_sum(q);
   return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, row16_max(t))));
 }
 // scale of dS for a wave whose own side has largest row norm^2 `own2` and whose streamed side is bounded by `other` per
 // element (both in plane units, 64 channels): dS * scale < 2^15
 __device__ __forceinline__ float ds_scale_x(float own2, float other) {
-  return plane_scale_x(2.f * __builtin_sqrtf(own2) * (8.f * other));
+  return plane_scale(2.f * __builtin_sqrtf(own2) * (8.f * other));
 }
 
 struct FmtXH : Fp32Storage {
@@ -642,11 +593,7 @@ struct FmtXH : Fp32Storage {
   static constexpr int dst_mcb(int) { return AMPCONV_XH_DST_MCB; }
 
   // (x0, x1), already scaled, |x| < 2^16 -> packed fp16 pairs of the two planes
-  static __device__ __forceinline__ void split(float x0, float x1, int (&w)[2]) {
-    w[0] = pk_h(x0, x1);
-    const f16x2 hv = __builtin_bit_cast(f16x2, w[0]);
-    w[1] = pk_h(x0 - (float)hv[0], x1 - (float)hv[1]);
-  }
+  static __device__ __forceinline__ void split(float x0, float x1, int (&w)[2]) { split2(x0, x1, w[0], w[1]); }
   static __device__ __forceinline__ f32x4 mma(const Frag &a, const Frag &b, f32x4 c) {      // planes hi, lo = p[0], p[1]
     c = MFMA_XH(a.p[1], b.p[0], c);
     c = MFMA_XH(a.p[0], b.p[1], c);
@@ -658,7 +605,7 @@ struct FmtXH : Fp32Storage {
   float sd, usd;            // this wave's scale of dS
   // (the forward pass reads bounds[0] only: include/ampconv.h)
   __device__ __forceinline__ FmtXH(const XArgs &a, bool grad)
-      : sq(plane_scale_x(a.bounds[0])), uq(1.f / sq), sg(grad ? plane_scale_x(a.bounds[1]) : 1.f), ug(1.f / sg),
+      : sq(plane_scale(a.bounds[0])), uq(1.f / sq), sg(grad ? plane_scale(a.bounds[1]) : 1.f), ug(1.f / sg),
         sc((a.qscale * uq) * uq), sd(1.f), usd(1.f) {}
   __device__ __forceinline__ float q_mul(const XArgs &) const { return sq; }
   __device__ __forceinline__ float g_mul(float inv) const { return inv * sg; }
@@ -710,7 +657,7 @@ struct FmtXB {
   static constexpr int fwd_mcb(int mct) { return mct; }
   static constexpr int dst_mcb(int mct) { return mct; }
 
-  static __device__ __forceinline__ void split(float x0, float x1, int (&w)[1]) { w[0] = pk_bf(x0, x1); }
+  static __device__ __forceinline__ void split(float x0, float x1, int (&w)[1]) { w[0] = cvt_pk_bf16(x0, x1); }
   static __device__ __forceinline__ f32x4 mma(const Frag &a, const Frag &b, f32x4 c) { return MFMA_X3(a.p[0], b.p[0], c); }
   template <int VEC, int MCT>
   static __device__ __forceinline__ float store(const ampconv_view_t &v, int64_t node, int h, const f32x4 (&T)[MCT], float scale,
@@ -739,7 +686,7 @@ struct FmtXB {
   __device__ __forceinline__ float dq_mul(const XArgs &a) const { return part_or(a, a.oscale); }
   // (partial tiles of a long column: the combine pass of this family multiplies dK by ln 2 -- its fp32 kernels carry
   // log2e / sqrt(dh) in Q --, so they leave with log2e / sqrt(dh) here)
-  __device__ __forceinline__ float dk_mul(const XArgs &a) const { return a.hub.mode == 2 ? a.oscale * kLog2eX : a.oscale; }
+  __device__ __forceinline__ float dk_mul(const XArgs &a) const { return a.hub.mode == 2 ? a.oscale * kLog2e : a.oscale; }
   __device__ __forceinline__ float dv_mul() const { return 1.f; }
 };
 
@@ -811,7 +758,7 @@ __device__ __forceinline__ void fwd_body(const XArgs &a) {
     Frag pf[NPAIR];
 #pragma unroll
     for (int mb = 0; mb < MCT / MCB; ++mb) {                  // MCB channel tiles per group of transposed reads
-      X3_PRE_READ();
+      TR_WAR_GUARD();
       Frag vc[MCB][NPAIR];
 #pragma unroll
       for (int u = 0; u < MCB; ++u)
@@ -821,7 +768,7 @@ __device__ __forceinline__ void fwd_body(const XArgs &a) {
 #pragma unroll
         for (int i = 0; i < NPAIR; ++i) pf[i] = cd_frag<Fmt, NT>(S, i);      // (in the shadow of the reads)
       }
-      X3_FRAG_FENCE();
+      TR_FRAG_FENCE();
 #pragma unroll
       for (int u = 0; u < MCB; ++u)
 #pragma unroll
@@ -919,7 +866,7 @@ __device__ __forceinline__ void bwd_dst_body(const XArgs &a) {
     Frag sf[NPAIR];
 #pragma unroll
     for (int mb = 0; mb < MCT / MCB; ++mb) {
-      X3_PRE_READ();
+      TR_WAR_GUARD();
       Frag kc[MCB][NPAIR];
 #pragma unroll
       for (int u = 0; u < MCB; ++u)
@@ -929,7 +876,7 @@ __device__ __forceinline__ void bwd_dst_body(const XArgs &a) {
 #pragma unroll
         for (int i = 0; i < NPAIR; ++i) sf[i] = cd_frag<Fmt, NT>(S, i);
       }
-      X3_FRAG_FENCE();
+      TR_FRAG_FENCE();
 #pragma unroll
       for (int u = 0; u < MCB; ++u)
 #pragma unroll
@@ -1032,13 +979,13 @@ __device__ __forceinline__ void bwd_src_body(const XArgs &a) {
         Frag pf, sf;
 #pragma unroll
         for (int mc = 0; mc < MCT; ++mc) {
-          X3_PRE_READ();
+          TR_WAR_GUARD();
           const Frag gc = colfrag<P, NT>(Gt, fa.tr[mc], i), qc = colfrag<P, NT>(Qt, fa.tr[mc], i);
           if (mc == 0) {
             pf = cd_frag<Fmt, 2>(Pw, 0);
             sf = cd_frag<Fmt, 2>(dS, 0);
           }
-          X3_FRAG_FENCE();
+          TR_FRAG_FENCE();
           dVT[mc] = Fmt::mma(gc, pf, dVT[mc]);
           dKT[mc] = Fmt::mma(qc, sf, dKT[mc]);
         }
@@ -1051,7 +998,7 @@ __device__ __forceinline__ void bwd_src_body(const XArgs &a) {
       Frag pf[NPAIR], sf[NPAIR];
 #pragma unroll
       for (int mc = 0; mc < MCT; ++mc) {
-        X3_PRE_READ();
+        TR_WAR_GUARD();
         Frag gc[NPAIR], qc[NPAIR];
 #pragma unroll
         for (int i = 0; i < NPAIR; ++i) {
@@ -1065,7 +1012,7 @@ __device__ __forceinline__ void bwd_src_body(const XArgs &a) {
             sf[i] = cd_frag<Fmt, NT>(dS, i);
           }
         }
-        X3_FRAG_FENCE();
+        TR_FRAG_FENCE();
 #pragma unroll
         for (int i = 0; i < NPAIR; ++i) {
           dVT[mc] = Fmt::mma(gc[i], pf[i], dVT[mc]);
@@ -1173,7 +1120,7 @@ struct XLaunch {
   XLaunch(XFmt fmt, int64_t n_rows, int L, int D, int H) : fmt(fmt) {
     a.L = L; a.dh = D / H; a.H = H;
     a.n_units = n_rows * H;
-    a.qscale = kLog2eX / sqrtf((float)a.dh);
+    a.qscale = kLog2e / sqrtf((float)a.dh);
   }
   // `views`: every view the kernel touches (they decide the vector width)
   int run(XPass pass, const ampconv_view_t *views, int n, hipStream_t stream) const {

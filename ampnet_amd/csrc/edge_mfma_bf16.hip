@@ -6,26 +6,20 @@
 // the fp32 oracle at bf16 tolerance (tests/test_gpu_parity.py::test_bf16_storage).
 //
 // Structure = edge_mfma_split.hip with ONE plane: a streamed 20 x 32 bf16 tile (64-byte token
-// rows, 16 rows per wave-wide 16-B/lane load) goes straight into the swizzled LDS plane image;
+// rows, 16 rows per wave-wide 16-B/lane load) goes straight into the swizzled LDS plane image (plane16.h);
 // channel-product fragments are one ds_read_b128, token-product fragments two
 // ds_read_b64_tr_b16 (hardware transpose), softmax results are converted to bf16 in registers
 // and are the B operand of the next product as they stand (tokens 16..19 sit in lane group 0).
 // Scales that the fp32 kernels fold into operands (log2e/sqrt(dh), 1/deg) are applied to the fp32
 // accumulators instead.  Long segments (hubs) reduce into fp32 partial tiles (hub.hip).
 #include <cstdlib>
-#include "mfma_tile.h"
+#include "plane16.h"
 
 namespace {
+using namespace plane16;      // conversions, the swizzled plane image (plane_off, rowfrag, colfrag), TR_FRAG_FENCE
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short bf16_t;
 
-constexpr float kLog2e = 1.4426950408889634f;
 constexpr int kWavesPerBlock = 4;
 constexpr int DH = 32;
 // HALF (dh = 16, BASELINE config 3's head width): the head's 16 channels occupy the lower half of a 32-channel tile;
@@ -36,18 +30,6 @@ constexpr int kTileBytes = kLmax * kRowBytes;     // 1280 B
 
 #define MFMA_BF16(a, b, c) \
   __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), (c), 0, 0, 0)
-
-__device__ __forceinline__ int cvt_pk_bf16(float a, float b) {
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(int, __builtin_convertvector(v, bf16x2));
-}
-
-// byte offset of 16-byte chunk `ch` (0..3) of token row `j` in the plane image (same swizzle as
-// edge_mfma_split.hip: conflict-free ds_write_b128 / ds_read_b128 / transposed reads)
-__device__ __forceinline__ int plane_off(int j, int ch) {
-  const int f = (4 - (j >> 2)) & 3;
-  return j * kRowBytes + ((ch ^ f) << 4);
-}
 
 // ---- streamed tile pair: lane (r = lane >> 2, q = lane & 3) owns 16 B (8 channels) of pair-rows
 // r, r + 16, r + 32 (< 40); pair-rows 0..19 = tile A, 20..39 = tile B
@@ -90,14 +72,8 @@ __device__ __forceinline__ void tiles_zero(char *tiles, int lane) {
   for (int i = lane; i < 2 * kTileBytes / 4; i += AMPCONV_WAVE) z[i] = 0;
 }
 
-// channel-product fragment of row tile mt from LDS.  Tile 1 uses the quarter map of mfma_tile.h:
-// MFMA row m <-> token 16 + (m >> 2), so in C/D layout lane group g holds token 16 + g in reg 0
-__device__ __forceinline__ i32x4 rowfrag(const char *tile, int mt, int lane) {
-  const int m = lane & 15, kg = lane >> 4;
-  const int j = mt == 0 ? m : 16 + (m >> 2);
-  return *reinterpret_cast<const i32x4 *>(tile + plane_off(j, kg));
-}
-// ... of column tile nt straight from global memory (fixed side; token rows >= L read as zero)
+// channel-product fragment (rowfrag: plane16.h) of column tile nt straight from global memory (fixed side; token rows
+// >= L read as zero)
 template <bool HALF>
 __device__ __forceinline__ i32x4 rowfrag_global(const bf16_t *base, int64_t row_stride, int nt, int L,
                                                 int lane) {
@@ -107,32 +83,9 @@ __device__ __forceinline__ i32x4 rowfrag_global(const bf16_t *base, int64_t row_
   if (j < L && (!HALF || kg < 2)) x = *reinterpret_cast<const i32x4 *>(base + (int64_t)j * row_stride + 8 * kg);
   return x;
 }
-// token-product fragment of channel tile mc: k-slots 0..3 = tokens 4kg..4kg+3, slot 4 = token 16 + kg
-// (slots 5..7 repeat it; the other operand holds zeros there)
-__device__ __forceinline__ i32x4 colfrag(const char *tile, int mc, int lane) {
-  const int q = (lane >> 2) & 3, pp = lane & 3, kg = lane >> 4;
-  const int ch = 2 * mc + (pp >> 1), half = (pp & 1) << 3;
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4 *)(tile + plane_off(4 * kg + q, ch) + half));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4 *)(tile + plane_off(16 + kg, ch) + half));
-  const i32x2 ai = __builtin_bit_cast(i32x2, a), bi = __builtin_bit_cast(i32x2, b);
-  return i32x4{ai[0], ai[1], bi[0], bi[1]};
-}
-// Every transposed fragment of a product group is in its registers before the group's first MFMA issues, and no
-// transposed read is scheduled in among the MFMAs: the interleaved schedule hipcc picks by itself -- an MFMA's operand
-// register redefined by the next ds_read_b64_tr_b16 right behind it, consumed right behind the wait -- gave wrong sums in
-// the weight-gradient kernel (csrc/proj_gemm.hip).  These kernels never showed it (thousands of bitwise
-// identical repeated steps), at 4-6 waves per SIMD the wait costs nothing measurable, so they carry the fence too.
-#ifdef AMPCONV_BF16_NOFENCE
+#ifdef AMPCONV_BF16_NOFENCE      // developer rebuild of THIS file's kernels without the fence
+#undef TR_FRAG_FENCE
 #define TR_FRAG_FENCE() do {} while (0)
-#else
-#define TR_FRAG_FENCE()                                    \
-  do {                                                     \
-    __builtin_amdgcn_sched_barrier(0);                     \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     \
-    __builtin_amdgcn_sched_barrier(0);                     \
-  } while (0)
 #endif
 // C/D registers -> token-product fragment (t1[1..3] must already be zero: only reg 0 of tile 1 is a token)
 __device__ __forceinline__ i32x4 cd_frag(const f32x4 &t0, const f32x4 &t1) {
@@ -527,12 +480,7 @@ __device__ __forceinline__ i32x4 rowfrag_global_q(const bf16_t *base, int64_t ro
 __device__ __forceinline__ i32x4 colfrag32(const char *tile, int blk, int lane) {
   const int q = (lane >> 2) & 3, pp = lane & 3, kg = lane >> 4;
   const int ch = 2 * blk + (pp >> 1), half = (pp & 1) << 3;
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4 *)(tile + plane_off(8 * kg + q, ch) + half));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4 *)(tile + plane_off(8 * kg + 4 + q, ch) + half));
-  const i32x2 ai = __builtin_bit_cast(i32x2, a), bi = __builtin_bit_cast(i32x2, b);
-  return i32x4{ai[0], ai[1], bi[0], bi[1]};
+  return tr_frag(tile + plane_off(8 * kg + q, ch) + half, tile + plane_off(8 * kg + 4 + q, ch) + half);
 }
 // a lane's column of a C/D tile pair (t0[q] = own token 4 g + q, t1_0 = own token 16 + g) -> row i of the transposed image
 __device__ __forceinline__ void file_column(char *img, int i, const f32x4 &t0, float t1_0, int g) {

@@ -1,6 +1,7 @@
 // fp32-grade edge kernels off the FP32 pipe (gfx950): Q/K/V and dObar arrive as TWO fp16 PLANES of the
 // power-of-two-scaled fp32 value (written that way by the projection that produces them: proj_gemm.hip, PLANES
-// epilogue), every product is the fp32 sum of three v_mfma_f32_16x16x32_f16 partial products
+// epilogue; scale and split are defined once for both sides, plane16.h), every product is the fp32 sum of three
+// v_mfma_f32_16x16x32_f16 partial products
 //      a b ~ a_lo b_hi + a_hi b_lo + a_hi b_hi        (dropped: a_lo b_lo <= 2^-22 |a b|)
 // softmax, delta and all sums stay fp32, outputs (Obar, dQ, dK, dV) are plain fp32.  Same bytes per element as the
 // fp32 path, 5 % of its matrix-pipe cycles per product (3 x 16 instead of 8 x 32 x 4 tiles), and the 16-bit matrix
@@ -17,26 +18,19 @@
 //
 // Structure = edge_mfma_bf16.hip with two plane images per tile: one wavefront owns one (row, head) unit, streams a
 // pair of 20 x 128-byte tiles per edge (five full wave-wide 16-B/lane loads) through registers into private LDS
-// images (per plane the swizzled 64-byte-row image of the bf16 kernels: conflict-free ds_write_b128, ds_read_b128 and
-// transposed reads), channel-product fragments are one ds_read_b128 per plane, token-product fragments two
+// images (per plane the swizzled 64-byte-row image of the bf16 kernels, plane16.h: conflict-free ds_write_b128,
+// ds_read_b128 and transposed reads), channel-product fragments are one ds_read_b128 per plane, token-product fragments two
 // ds_read_b64_tr_b16 per plane, softmax results are split into two fp16 planes in registers and are the B operand of
 // the next product as they stand.  dObar arrives DIVIDED by the in-degree of its node (the producing projection's
 // epilogue does it), so neither backward pass carries a per-edge weight.  Softmax statistics (optional, as in the fp32
 // kernels: 20 log2-sum-exp + 20 delta floats per edge and head, filed at the edge's CSC position by the destination pass):
 // with them the source pass's softmax is element-wise -- its three 16-lane reductions per row are a third of its
 // vector instructions, and these passes are bound by vector issue and by the clock the chip holds under them.
-#include "mfma_tile.h"
+#include "plane16.h"
 
 namespace {
+using namespace plane16;      // plane_scale, split2, frag_sumsq, the swizzled plane image (plane_off, rowfrag, colfrag), TR_*
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-constexpr float kLog2e = 1.4426950408889634f;
 constexpr int kWavesPerBlock = 4;
 constexpr int DH = 32;
 // HALF (dh = 16, BASELINE config 3's head width): the head's slot is 64 bytes (16 hi, 16 lo); its 16 channels occupy the
@@ -73,35 +67,6 @@ __device__ __forceinline__ f32x4 mfma3(const i32x4 &ah, const i32x4 &al, const i
   return MFMA_F16(ah, bh, c);
 }
 
-// scale of a tensor whose magnitudes are bounded by `bound` (the function of proj_gemm.hip: both sides of the hand-off
-// must derive the same power of two): 2^(14 - floor(log2 bound)), exponent field clamped to [15, 254]
-__device__ __forceinline__ float plane_scale(float bound) {
-  int e = (int)((__builtin_bit_cast(unsigned, bound) >> 23) & 0xFFu);
-  e = e < 15 ? 15 : (e > 254 ? 254 : e);
-  return __builtin_bit_cast(float, (unsigned)(268 - e) << 23);
-}
-
-__device__ __forceinline__ int cvt_pk_f16(float a, float b) {      // v_cvt_pk_f16_f32 (RNE)
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(int, __builtin_convertvector(v, f16x2));
-}
-// (x0, x1) -> packed fp16 pairs of the two planes; |x| < 2^16
-__device__ __forceinline__ void split2(float x0, float x1, int &h, int &l) {
-  h = cvt_pk_f16(x0, x1);
-  const f16x2 hv = __builtin_bit_cast(f16x2, h);
-  l = cvt_pk_f16(x0 - (float)hv[0], x1 - (float)hv[1]);
-}
-
-// sum of squares of the 8 fp16 values of a fragment register quadruple (v_dot2_f32_f16)
-__device__ __forceinline__ float frag_sumsq(const i32x4 &f) {
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const f16x2 v = __builtin_bit_cast(f16x2, f[k]);
-    s = __builtin_amdgcn_fdot2(v, v, s, false);
-  }
-  return s;
-}
 // largest token-row norm^2 of a tile given as its two channel-product fragments (lane (n, kg) = 8 channels of the token
 // of column n): wave-uniform
 __device__ __forceinline__ float tile_max_norm2(const i32x4 &f0, const i32x4 &f1) {
@@ -112,12 +77,6 @@ __device__ __forceinline__ float tile_max_norm2(const i32x4 &f0, const i32x4 &f1
 // per element (both in plane units): dS * scale < 2^15
 __device__ __forceinline__ float ds_scale(float own2, float other) {
   return plane_scale(2.f * __builtin_sqrtf(own2) * (kSqrtDh * other));
-}
-
-// byte offset of 16-byte chunk `ch` (0..3) of token row `j` in a plane image (the swizzle of edge_mfma_bf16.hip)
-__device__ __forceinline__ int plane_off(int j, int ch) {
-  const int f = (4 - (j >> 2)) & 3;
-  return j * kRowBytes + ((ch ^ f) << 4);
 }
 
 // ---- streamed tile pair: lane (r = lane >> 3, q = lane & 7) owns 16-byte chunk q (0..3: hi plane, 4..7: lo plane) of
@@ -163,15 +122,9 @@ __device__ __forceinline__ void lds_zero(char *p, int bytes, int lane) {
   for (int i = lane; i < bytes / 4; i += AMPCONV_WAVE) z[i] = 0;
 }
 
-// channel-product fragment of row tile mt of ONE plane image.  Tile 1 uses the quarter map of mfma_tile.h: MFMA row m
-// <-> token 16 + (m >> 2), so in C/D layout lane group g holds token 16 + g in reg 0
-__device__ __forceinline__ i32x4 rowfrag(const char *img, int mt, int lane) {
-  const int m = lane & 15, kg = lane >> 4;
-  const int j = mt == 0 ? m : 16 + (m >> 2);
-  return *reinterpret_cast<const i32x4 *>(img + plane_off(j, kg));
-}
-// ... of column tile nt straight from global memory (the unit's own side, once per unit; plain map: column m of tile 1
-// is token 16 + m; token rows >= L read as zero).  `base` = the row-0 slot of the (node, head), `plane` = 0 / 64
+// channel-product fragment (rowfrag: plane16.h, of ONE plane image) of column tile nt straight from global memory (the
+// unit's own side, once per unit; plain map: column m of tile 1 is token 16 + m; token rows >= L read as zero).
+// `base` = the row-0 slot of the (node, head), `plane` = 0 / 64
 template <bool HALF>
 __device__ __forceinline__ i32x4 rowfrag_global(const char *base, unsigned row_bytes, int nt, int plane, int L, int lane) {
   const int m = lane & 15, kg = lane >> 4;
@@ -180,41 +133,6 @@ __device__ __forceinline__ i32x4 rowfrag_global(const char *base, unsigned row_b
   if (j < L && (!HALF || kg < 2)) x = *reinterpret_cast<const i32x4 *>(base + (unsigned)j * row_bytes + plane + 16 * kg);
   return x;
 }
-// token-product fragment of channel tile mc of ONE plane image: k-slots 0..3 = tokens 4 kg .. 4 kg + 3, slot 4 = token
-// 16 + kg (slots 5..7 repeat it; the other operand holds zeros there)
-__device__ __forceinline__ i32x4 colfrag(const char *img, int mc, int lane) {
-  const int q = (lane >> 2) & 3, pp = lane & 3, kg = lane >> 4;
-  const int ch = 2 * mc + (pp >> 1), half = (pp & 1) << 3;
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4 *)(img + plane_off(4 * kg + q, ch) + half));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4 *)(img + plane_off(16 + kg, ch) + half));
-  const i32x2 ai = __builtin_bit_cast(i32x2, a), bi = __builtin_bit_cast(i32x2, b);
-  return i32x4{ai[0], ai[1], bi[0], bi[1]};
-}
-// every transposed fragment of a product group is in its registers before the group's first MFMA issues, and no
-// transposed read is scheduled in among the MFMAs (the fence of proj_gemm.hip / edge_mfma_bf16.hip; tests/test_abi.py
-// scans the shipped ISA for the pattern)
-#define TR_FRAG_FENCE()                                    \
-  do {                                                     \
-    __builtin_amdgcn_sched_barrier(0);                     \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     \
-    __builtin_amdgcn_sched_barrier(0);                     \
-  } while (0)
-
-// behind a group of MFMAs whose fragment registers the next group's transposed reads may take over: the last MFMA has
-// fetched its operands before a read redefines them (tools/scan_tr_hazard.py --gate, rule WAR)
-#define TR_WAR_GUARD()                         \
-  do {                                         \
-    __builtin_amdgcn_sched_barrier(0);         \
-    asm volatile("s_nop 7" ::: "memory");      \
-    __builtin_amdgcn_sched_barrier(0);         \
-  } while (0)
-
-// in front of a group of transposed reads that follows MFMAs of another phase (their fragment registers may be taken
-// over): eight idle cycles and a compiler barrier for memory operations only -- the vector work around it still moves
-#define TR_PRE_READ() asm volatile("s_nop 7" ::: "memory")
-
 // C/D registers (already in the split's units, |x| < 2^16) -> the two planes of a token-product fragment: slots 0..3 =
 // t0 (tokens 4 g + q), slot 4 = t1_0 (token 16 + g), slots 5..7 zero
 __device__ __forceinline__ void cd_frag2(const f32x4 &t0, float t1_0, i32x4 &hi, i32x4 &lo) {

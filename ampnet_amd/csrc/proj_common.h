@@ -1,35 +1,20 @@
 // Shared pieces of the node-phase projection kernels (proj_gemm.hip: fp32 storage, proj_gemm_bf16.hip: bf16 storage).
+// The plane format itself (conversions, scale, split, transposed-read fragments and their fences): plane16.h.
 #pragma once
-#include "common.h"
+#include "plane16.h"
 
 namespace proj {
+using namespace plane16;
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) char lds_char;
 
 constexpr int kFrag = 1024;          // one MFMA operand fragment: 64 lanes x 8 bf16
 constexpr int kXcd = 8;
 
-__device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {   // v_cvt_pk_bf16_f32 (RNE)
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
 __device__ __forceinline__ float lo_as_f32(unsigned h) { return __builtin_bit_cast(float, h << 16); }
 __device__ __forceinline__ float hi_as_f32(unsigned h) { return __builtin_bit_cast(float, h & 0xFFFF0000u); }
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned cvt_pk_f16(float a, float b) {    // v_cvt_pk_f16_f32 (RNE)
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));
-}
 #define MFMA32H(a, b, c)                                                                                         \
   __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(proj::f16x8, a), __builtin_bit_cast(proj::f16x8, b), \
                                          (c), 0, 0, 0)
@@ -50,15 +35,6 @@ __device__ __forceinline__ void dma16(const void *gsrc, unsigned lds_dst) {
                : "memory");
 }
 
-// two transposing 8-byte LDS reads = one 32x32x16 operand fragment whose 8 consecutive k per lane are ROWS of a
-// row-major bf16 image (ds_read_b64_tr_b16: 4 rows x 16 columns per 16 lanes, delivered column-major)
-__device__ __forceinline__ i32x4 tr_frag(const char *p0, const char *p1) {
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)p0);
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)p1);
-  const i32x2 ai = __builtin_bit_cast(i32x2, a), bi = __builtin_bit_cast(i32x2, b);
-  return i32x4{ai[0], ai[1], bi[0], bi[1]};
-}
-
 inline int cu_count() {
   static const int n_cu = [] {
     int dev = 0, n = 256;
@@ -66,6 +42,95 @@ inline int cu_count() {
     return n;
   }();
   return n_cu;
+}
+
+// ---- the second step of both weight-gradient products: out[e] = sum over the slices of part[s][e]; e < n_dw goes to dW,
+// the rest to colsum.  256 threads = 32 float4 elements x 8 slice phases: phase g adds slices g, g + 8, ... in order (four
+// loads in flight), the eight phase sums meet in LDS and are added in a fixed order -- bitwise reproducible, and S / 8
+// dependent load rounds instead of S.  `Out` is the epilogue: where four sums of dW / of the column sums go, and as what.
+struct ReduceF32 {      // fp32 out; scaled mode (amax_a / amax_b non-null): the dW part leaves through the two exact inverse scales
+  float *dW, *colsum;
+  const float *amax_a, *amax_b;
+  __device__ __forceinline__ void dw(float4 acc, size_t o) const {
+    if (amax_a) {
+      const float ua = plane_unscale(*amax_a), ub = plane_unscale(*amax_b);
+      acc.x = acc.x * ua * ub; acc.y = acc.y * ua * ub; acc.z = acc.z * ua * ub; acc.w = acc.w * ua * ub;
+    }
+    *reinterpret_cast<float4 *>(dW + o) = acc;
+  }
+  __device__ __forceinline__ void cs(float4 acc, size_t o) const { *reinterpret_cast<float4 *>(colsum + o) = acc; }
+};
+struct ReduceBf16 {     // one rounding to bf16 on the way out
+  unsigned short *dW, *colsum;
+  static __device__ __forceinline__ i32x2 pack(float4 acc) { return i32x2{cvt_pk_bf16(acc.x, acc.y), cvt_pk_bf16(acc.z, acc.w)}; }
+  __device__ __forceinline__ void dw(float4 acc, size_t o) const { *reinterpret_cast<i32x2 *>(dW + o) = pack(acc); }
+  __device__ __forceinline__ void cs(float4 acc, size_t o) const { *reinterpret_cast<i32x2 *>(colsum + o) = pack(acc); }
+};
+template <class Out>
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restrict__ part, int S, int Na, int Nb, int Nap,
+                                                           int Nbp, Out out) {
+  __shared__ float4 red[8][32];
+  const int el = threadIdx.x & 31, g = threadIdx.x >> 5;
+  const int64_t n_dw = (int64_t)Nap * Nbp, n_all = n_dw + Nap;        // the slabs cover the padded shape
+  const int64_t e = ((int64_t)blockIdx.x * 32 + el) * 4;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (e < n_all) {
+    float4 a1 = acc;
+    int s = g;
+    for (; s + 8 < S; s += 16) {
+      const float4 v0 = *reinterpret_cast<const float4 *>(part + (size_t)s * n_all + e);
+      const float4 v1 = *reinterpret_cast<const float4 *>(part + (size_t)(s + 8) * n_all + e);
+      acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
+      a1.x += v1.x; a1.y += v1.y; a1.z += v1.z; a1.w += v1.w;
+    }
+    if (s < S) {
+      const float4 v0 = *reinterpret_cast<const float4 *>(part + (size_t)s * n_all + e);
+      acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
+    }
+    acc.x += a1.x; acc.y += a1.y; acc.z += a1.z; acc.w += a1.w;
+  }
+  red[g][el] = acc;
+  __syncthreads();
+  if (g == 0 && e < n_all) {
+#pragma unroll
+    for (int k = 1; k < 8; ++k) {
+      const float4 v = red[k][el];
+      acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+    }
+    if (e < n_dw) {
+      const int i = (int)(e / Nbp), j = (int)(e - (int64_t)i * Nbp);
+      if (i < Na && j < Nb) out.dw(acc, (size_t)i * Nb + j);
+    } else if (out.colsum && e - n_dw < Na) {
+      out.cs(acc, (size_t)(e - n_dw));
+    }
+  }
+}
+
+// ---- the first step's shape: tile of dW and row slices, for `rows_per_stage` rows per pipeline stage (kRS / kRSB)
+struct WgradPlan {
+  int S;
+  int64_t rows_per_slice;      // a multiple of rows_per_stage
+  int ti, tj;
+};
+// padded shape (multiples of 128).  256 x 256: eight waves, one workgroup per CU; the others: four waves, two per CU.
+// `square`: the kernel has T x T tiles only (bf16 storage), else 128 x 256 exists too (Na an odd multiple of 128)
+inline WgradPlan wgrad_plan(int64_t M, int Nap, int Nbp, int rows_per_stage, bool square) {
+  WgradPlan p;
+  p.tj = Nbp % 256 == 0 ? 256 : 128;
+  p.ti = (Nap % 256 == 0 && p.tj == 256) ? 256 : 128;
+  if (square) p.tj = p.ti;
+  const int64_t ntiles = (int64_t)(Nap / p.ti) * (Nbp / p.tj);
+  const int64_t nstages = (M + rows_per_stage - 1) / rows_per_stage;
+  // one round of workgroups: slices are dealt to the 8 XCDs in turn (round-robin dispatch) and every slice brings
+  // `ntiles` workgroups, so an XCD's 32 CUs (x 2 for the 4-wave shapes) hold floor(32 / ntiles) slices each --
+  // one slice more on some XCDs would run as a second round and double the time
+  const int per_xcd = (p.ti == 256 ? 1 : 2) * 32;
+  int64_t S = (int64_t)kXcd * (per_xcd / ntiles > 0 ? per_xcd / ntiles : 1);
+  if (S > nstages) S = nstages > 0 ? nstages : 1;
+  p.rows_per_slice = ((nstages + S - 1) / S) * rows_per_stage;
+  p.S = (int)((M + p.rows_per_slice - 1) / p.rows_per_slice);
+  if (p.S < 1) p.S = 1;
+  return p;
 }
 
 }  // namespace proj

@@ -31,7 +31,9 @@
 //   proj_wgrad dW[Na, Nb] = A[M, Na]^T B[M, Nb], colsum(A)         (weight / bias gradients: reduction over
 //              the N*L node-token rows; both operands split on the fly, fragments by the hardware-transposing
 //              ds_read_b64_tr_b16; deterministic two-step reduction over row slices)
-#include <stdlib.h>
+// The plane format itself (scale, two-plane split, transposed-read fragments and their fences): plane16.h.  The second step
+// of proj_wgrad and its slice plan, shared with the bf16 kernels: proj_common.h.  ampconv_absmax and the other
+// operand-range helpers of the scaled mode: operand_scale.hip.
 #include <type_traits>
 #include "proj_common.h"
 
@@ -54,36 +56,23 @@ __device__ __forceinline__ f32x16 mfma_p(const i32x4 &a, const i32x4 &b, const f
   else return MFMA32(a, b, c);
 }
 
-// scale of a tensor whose largest finite magnitude is `amax`: 2^(14 - floor(log2 amax)), so that the scaled maximum
-// lies in [2^14, 2^15) (fp16: finite below 2^16); exponent field clamped to [15, 254] (zero / subnormal maxima take
-// 2^126, a non-finite one -- never produced by ampconv_absmax -- 2^-113)
-__device__ __forceinline__ float plane_scale(float amax) {
-  int e = (int)((__builtin_bit_cast(unsigned, amax) >> 23) & 0xFFu);
-  e = e < 15 ? 15 : (e > 254 ? 254 : e);
-  return __builtin_bit_cast(float, (unsigned)(268 - e) << 23);
-}
-__device__ __forceinline__ float plane_unscale(float amax) { return 1.f / plane_scale(amax); }     // exact: a power of two
-
 // (x0, x1) -> packed bf16 pairs of the three planes; x == h1 + h2 + h3 exactly
 struct Pair3 {
   int h1, h2, h3;
 };
 __device__ __forceinline__ Pair3 split_pair(float x0, float x1) {
-  const unsigned a = cvt_pk_bf16(x0, x1);
+  const unsigned a = (unsigned)cvt_pk_bf16(x0, x1);
   const float r0 = x0 - lo_as_f32(a), r1 = x1 - hi_as_f32(a);
-  const unsigned b = cvt_pk_bf16(r0, r1);
+  const unsigned b = (unsigned)cvt_pk_bf16(r0, r1);
   const float s0 = r0 - lo_as_f32(b), s1 = r1 - hi_as_f32(b);
-  return Pair3{(int)a, (int)b, (int)cvt_pk_bf16(s0, s1)};
+  return Pair3{(int)a, (int)b, cvt_pk_bf16(s0, s1)};
 }
 
-// (x0, x1) * s -> packed fp16 pairs of the two planes (h3 unused)
+// (x0, x1) * s -> packed fp16 pairs of the two planes (h3 unused): scale, then split (plane16.h)
 __device__ __forceinline__ Pair3 split_pair_h(float x0, float x1, float s) {
-  x0 *= s;
-  x1 *= s;
-  const unsigned a = cvt_pk_f16(x0, x1);
-  const f16x2 av = __builtin_bit_cast(f16x2, a);
-  const float r0 = x0 - (float)av[0], r1 = x1 - (float)av[1];
-  return Pair3{(int)a, (int)cvt_pk_f16(r0, r1), 0};
+  int h, l;
+  split2(x0 * s, x1 * s, h, l);
+  return Pair3{h, l, 0};
 }
 template <bool HP>
 __device__ __forceinline__ Pair3 split_pair_t(float x0, float x1, float s) {
@@ -101,23 +90,6 @@ __device__ __forceinline__ void mfma_row(const i32x4 (&a)[3], const i32x4 (&b)[N
 #pragma unroll
     for (int j = 0; j < NJ; ++j) c[j] = mfma_p<HP>(a[kPA[HP][q]], b[j][kPB[HP][q]], c[j]);
 }
-
-#ifdef AMPCONV_PROJ_STAMPS
-// diagnostic build (tools/stamp_proj.py): per-phase s_memtime sums of proj_rows_kernel, written to a device
-// buffer that nothing else reads; never part of the product build
-__device__ unsigned long long g_proj_stamps[8 * 4096];
-#define PSTAMP_DECL unsigned long long st_last, st_now, st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; \
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_last)::"memory");
-#define PSTAMP(i) do { __builtin_amdgcn_sched_barrier(0); \
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_now)::"memory"); \
-  __builtin_amdgcn_sched_barrier(0); st_acc[i] += st_now - st_last; st_last = st_now; } while (0)
-#define PSTAMP_FLUSH(unit) do { if ((unit) < 4096 && threadIdx.x == 0) for (int i_ = 0; i_ < 8; ++i_) \
-  g_proj_stamps[(unit) * 8 + i_] = st_acc[i_]; } while (0)
-#else
-#define PSTAMP_DECL
-#define PSTAMP(i)
-#define PSTAMP_FLUSH(unit)
-#endif
 
 // ---------------------------------------------------------------------------------------------------
 // weight image: for k step ks (16 deep), 32-column tile n32 of the OUTPUT, plane p:
@@ -215,7 +187,7 @@ __global__ void weight_image_kernel(ImageJobs jobs) {
 // buffer, so a wave's vector / LDS / memory instructions sit in the shadow of its own and its SIMD partner's MFMAs.
 // Workgroups are PERSISTENT: one flat step loop over a strided list of tiles, the first fragments of the next tile
 // are on their way before the store tail of the current one.
-// What the shape is chosen by (in-kernel stamps, tools/stamp_proj.py): every vector-memory instruction a wave
+// What the shape is chosen by (in-kernel stamps of a diagnostic build, git history has it): every vector-memory instruction a wave
 // issues (1-KiB row load, 1-KiB LDS-DMA piece, store) costs it ~100 cycles once all waves of a CU use the address
 // path, against 32 per MFMA: a 128 x 128 tile of four waves needs 0.38 of them per MFMA, 128 x 256 needs 0.19.
 // Output tiles leave through LDS as whole 128-byte row segments (dwordx4 stores: a quarter of the store
@@ -248,11 +220,8 @@ struct RowsArgs {
 
 // RAGGED: K % 32 != 0 or N % BN != 0 (e.g. the reference's default embed_dim = 100): row loads beyond K read as zero,
 // columns beyond N are computed on the image's zero padding and not stored
-#ifndef AMPCONV_PROJ_ROWS_128_WAVES
-#define AMPCONV_PROJ_ROWS_128_WAVES 2      // (A/B: 3 = the 128 x 128 scaled shapes compiled for three workgroups per CU)
-#endif
 template <int BM, int BN, int WM, int WN, bool RAGGED, bool HP, bool PLANES = false>
-__global__ __launch_bounds__(64 * WM * WN, (BM == 128 && BN == 128 && HP) ? AMPCONV_PROJ_ROWS_128_WAVES : 2) void proj_rows_kernel(RowsArgs a) {
+__global__ __launch_bounds__(64 * WM * WN, 2) void proj_rows_kernel(RowsArgs a) {
   static_assert(!PLANES || HP, "plane output exists in the scaled mode only");
   constexpr int kNP = Pl<HP>::NP, kTile3 = Pl<HP>::kTile;
   constexpr int NW = WM * WN, NTHR = 64 * NW;
@@ -420,7 +389,6 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 128 && BN == 128 && HP) ? AMPC
     }
   };
 
-  PSTAMP_DECL
   int64_t u = blockIdx.x;
   Tile cur = tile_of(u);
   if (!cur.valid) return;        // slots are ordered: nothing further for this workgroup either
@@ -455,9 +423,7 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 128 && BN == 128 && HP) ? AMPC
     for (int kb = 0; kb < KB; ++kb) {
       // ---- even step (fragments in buffer 0): the odd step's weight fragments by DMA, its rows = the second half
       // of the line block in registers; then the block is used up and the next one is requested
-      PSTAMP(0);
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // buffer 0 complete, buffer 1 free
-      PSTAMP(1);
       dma_step(cur, 2 * kb + 1, 1);
       compute(0);
       split_rows(std::integral_constant<int, 1>{}, 1, kpos - 32);       // (its half landed with the last full wait)
@@ -471,11 +437,9 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 128 && BN == 128 && HP) ? AMPC
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
-      PSTAMP(2);
       // ---- odd step (buffer 1): next even step's fragments (this tile's, or step 0 of the next tile; past the
       // end of the work list the refill is harmless and keeps the step free of branches)
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      PSTAMP(3);
       dma_step(last ? (nxt.valid ? nxt : cur) : cur, last ? 0 : 2 * kb + 2, 0);
       compute(1);
       // the row block requested in the even step (older than this step's DMA pieces, which stay in flight)
@@ -484,7 +448,6 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 128 && BN == 128 && HP) ? AMPC
       split_rows(std::integral_constant<int, 0>{}, 0, kpos - 32);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       ROWS_LANDED(1);
-      PSTAMP(4);
     }
     // store tail.  C/D register e of lane (col = lane & 31, hi = lane >> 5) is row (e & 3) + 8 (e >> 2) + 4 hi of a
     // 32 x 32 tile: bias and row mask applied in that layout, then the tile goes through a wave-private 4 KiB of
@@ -590,7 +553,6 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 128 && BN == 128 && HP) ? AMPC
           store_tile(std::true_type{});
       }
     }
-    PSTAMP(6);
     if (!nxt.valid) break;
     cur = nxt;
     u += gridDim.x;
@@ -603,7 +565,6 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 128 && BN == 128 && HP) ? AMPC
     for (int o = 32; o > 0; o >>= 1) omax = fmaxf(omax, __shfl_xor(omax, o));
     if (lane == 0) atomicMax(reinterpret_cast<unsigned *>(a.out_amax), __builtin_bit_cast(unsigned, omax));
   }
-  PSTAMP_FLUSH(blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -614,7 +575,7 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 128 && BN == 128 && HP) ? AMPC
 // chunk index XORed with (row & 3) makes both the 8-byte plane stores and the transposed reads conflict-free.
 // One 128 x TJ tile of dW per 256-thread workgroup and row slice; 16 rows per stage, two LDS buffers, one
 // barrier per stage, the next stage's rows in flight in registers.  Partial tiles per slice go to the
-// workspace and are added in slice order by wgrad_reduce_kernel (bitwise reproducible, no atomics).
+// workspace and are added in slice order by wgrad_reduce_kernel (proj_common.h: bitwise reproducible, no atomics).
 struct WgradArgs {
   const float *A;
   int64_t lda;
@@ -779,15 +740,12 @@ __global__ __launch_bounds__(64 * WI * WJ, 2) void proj_wgrad_kernel(WgradArgs a
         for (int p = 0; p < kNP; ++p) af[ii][p] = tr_frag(r0 + p * kPlaneA, r0 + p * kPlaneA + 4 * kRowA);
       }
       // Every fragment of the round is in its registers before the round's first MFMA issues, and no fragment read is
-      // scheduled in among the MFMAs.  Left to itself hipcc interleaves them and re-uses an operand register for the next
-      // fragment right behind the MFMA that reads it (`v_mfma .. v[128:131] ..; ds_read_b64_tr_b16 v[128:129] ..;
-      // s_waitcnt lgkmcnt(0); v_mfma .. v[128:131]`); builds with that schedule gave WRONG sums in 7-100 % of the launches
-      // of the masked product (one 16-bit element of a fragment stale; flags, rows and the LDS image verified correct
-      // at the barrier by an in-kernel dump: DESIGN.md 4a), with this fence 0 of 1 600.  -DAMPCONV_WG_NOFENCE rebuilds it.
+      // scheduled in among the MFMAs (plane16.h: left to itself hipcc interleaves them -- `v_mfma .. v[128:131] ..;
+      // ds_read_b64_tr_b16 v[128:129] ..; s_waitcnt lgkmcnt(0); v_mfma .. v[128:131]` -- and THIS kernel then gave wrong
+      // sums; flags, rows and the LDS image verified correct at the barrier by an in-kernel dump: DESIGN.md 4a).
+      // -DAMPCONV_WG_NOFENCE rebuilds the kernel without its fences.
 #ifndef AMPCONV_WG_NOFENCE
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 7\n\ts_nop 7" ::: "memory");      // (+ 16 idle cycles behind the wait)
-      __builtin_amdgcn_sched_barrier(0);
+      TR_FRAG_FENCE_IDLE();
 #endif
 #pragma unroll
       for (int q = 0; q < Pl<HP>::NQ; ++q)
@@ -797,11 +755,8 @@ __global__ __launch_bounds__(64 * WI * WJ, 2) void proj_wgrad_kernel(WgradArgs a
           for (int j = 0; j < NJW; ++j)
             acc[i + ii][j] = mfma_p<HP>(af[ii][kPA[HP][q]], bf[j][kPB[HP][q]], acc[i + ii][j]);
 #ifndef AMPCONV_WG_NOFENCE
-      // ... and the next round's (or stage's) reads do not redefine af[] / bf[] right behind the MFMA that reads them: the
-      // last MFMA of the round has fetched its operands by then (8 idle cycles; tools/scan_tr_hazard.py --gate, rule WAR)
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_nop 7" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
+      // ... and the next round's (or stage's) reads do not redefine af[] / bf[] right behind the MFMA that reads them
+      TR_WAR_GUARD();
 #endif
     }
   };
@@ -846,83 +801,6 @@ __global__ __launch_bounds__(256) void row_mask_kernel(const int32_t *__restrict
   const float f = rowptr[n + 1] != rowptr[n] ? 1.f : 0.f;
   const int64_t m0 = n * L;
   for (int l = 0; l < L && m0 + l < M; ++l) flag[m0 + l] = f;
-}
-
-// out[e] = sum over the slices of part[s][e]; e < n_dw goes to dW, the rest to colsum.  256 threads = 32 float4
-// elements x 8 slice phases: phase g adds slices g, g + 8, ... in order (four loads in flight), the eight phase sums
-// meet in LDS and are added in a fixed order -- bitwise reproducible, and S / 8 dependent load rounds instead of S
-// (scaled mode: amax_a / amax_b non-null, the dW part leaves through the two exact inverse scales)
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restrict__ part, int S, int Na, int Nb, int Nap,
-                                                           int Nbp, float *__restrict__ dW, float *__restrict__ colsum,
-                                                           const float *__restrict__ amax_a,
-                                                           const float *__restrict__ amax_b) {
-  __shared__ float4 red[8][32];
-  const int el = threadIdx.x & 31, g = threadIdx.x >> 5;
-  const int64_t n_dw = (int64_t)Nap * Nbp, n_all = n_dw + Nap;        // the slabs cover the padded shape
-  const int64_t e = ((int64_t)blockIdx.x * 32 + el) * 4;
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (e < n_all) {
-    float4 a1 = acc;
-    int s = g;
-    for (; s + 8 < S; s += 16) {
-      const float4 v0 = *reinterpret_cast<const float4 *>(part + (size_t)s * n_all + e);
-      const float4 v1 = *reinterpret_cast<const float4 *>(part + (size_t)(s + 8) * n_all + e);
-      acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
-      a1.x += v1.x; a1.y += v1.y; a1.z += v1.z; a1.w += v1.w;
-    }
-    if (s < S) {
-      const float4 v0 = *reinterpret_cast<const float4 *>(part + (size_t)s * n_all + e);
-      acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
-    }
-    acc.x += a1.x; acc.y += a1.y; acc.z += a1.z; acc.w += a1.w;
-  }
-  red[g][el] = acc;
-  __syncthreads();
-  if (g == 0 && e < n_all) {
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-      const float4 v = red[k][el];
-      acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-    }
-    if (e < n_dw) {
-      const int i = (int)(e / Nbp), j = (int)(e - (int64_t)i * Nbp);
-      if (amax_a) {
-        const float ua = plane_unscale(*amax_a), ub = plane_unscale(*amax_b);
-        acc.x = acc.x * ua * ub; acc.y = acc.y * ua * ub; acc.z = acc.z * ua * ub; acc.w = acc.w * ua * ub;
-      }
-      if (i < Na && j < Nb) *reinterpret_cast<float4 *>(dW + (size_t)i * Nb + j) = acc;
-    } else if (colsum && e - n_dw < Na) {
-      *reinterpret_cast<float4 *>(colsum + (e - n_dw)) = acc;
-    }
-  }
-}
-
-struct WgradPlan {
-  int S;
-  int64_t rows_per_slice;
-  int ti, tj;
-};
-inline WgradPlan wgrad_plan(int64_t M, int Nap, int Nbp) {       // padded shape (multiples of 128)
-  WgradPlan p;
-  static const bool small_ti = [] {                        // developer switch: 128 x 256 tiles of four waves, two per CU
-    const char *e = getenv("AMPCONV_PROJ_WGRAD_TI");
-    return e && atoi(e) == 128;
-  }();
-  p.tj = Nbp % 256 == 0 ? 256 : 128;
-  p.ti = (Nap % 256 == 0 && p.tj == 256 && !small_ti) ? 256 : 128;       // 256 x 256: eight waves, one workgroup per CU
-  const int64_t ntiles = (int64_t)(Nap / p.ti) * (Nbp / p.tj);
-  const int64_t nstages = (M + kRS - 1) / kRS;
-  // one round of workgroups: slices are dealt to the 8 XCDs in turn (round-robin dispatch) and every slice brings
-  // `ntiles` workgroups, so an XCD's 32 CUs (x 2 for the 4-wave shapes) hold floor(32 / ntiles) slices each --
-  // one slice more on some XCDs would run as a second round and double the time
-  const int per_xcd = (p.ti == 256 ? 1 : 2) * 32;
-  int64_t S = (int64_t)kXcd * (per_xcd / ntiles > 0 ? per_xcd / ntiles : 1);
-  if (S < 1) S = 1;
-  if (S > nstages) S = nstages > 0 ? nstages : 1;
-  p.rows_per_slice = ((nstages + S - 1) / S) * kRS;
-  p.S = (int)((M + p.rows_per_slice - 1) / p.rows_per_slice);
-  if (p.S < 1) p.S = 1;
-  return p;
 }
 
 }  // namespace
@@ -983,16 +861,11 @@ static int proj_rows_f32(const void *A_, int64_t lda, int64_t M, int K, const vo
   if (!A || !wimage || !out || (uintptr_t)A % 16 || (uintptr_t)wimage % 16) return AMPCONV_E_BADARG;
   if (rowptr && (L <= 0 || M > 0x7fffffff)) return AMPCONV_E_BADARG;
   if (ldc % 4 || (uintptr_t)out % 16) return AMPCONV_E_BADARG;
-  // tile shape (developer switch AMPCONV_PROJ_ROWS: 0 = 128 x 256 tile of 4 waves where N allows, 1 = 256 x 256 of 8)
-  static const int variant = [] {
-    const char *e = getenv("AMPCONV_PROJ_ROWS");
-    return e ? atoi(e) : 0;
-  }();
+  // tile: 128 rows x 256 columns where N allows, else 128 x 128; four waves, two workgroups per CU
   const int Np = (N + 127) / 128 * 128, Kp = (K + 31) / 32 * 32;
   const bool ragged = Np != N || Kp != K;
-  const int shape = (Np % 256 || variant == 2) ? 2 : variant;      // 0: 128 x 256 / 4 waves, 1: 256 x 256 / 8 waves, 2: 128 x 128 / 4 waves
-  const int bm = shape == 1 ? 256 : 128, bn = shape == 2 ? 128 : 256;
-  const int64_t rts = (M + bm - 1) / bm;
+  const int bn = Np % 256 ? 128 : 256;
+  const int64_t rts = (M + 127) / 128;
   if (rts > (int64_t)INT32_MAX / 64) return AMPCONV_E_BADARG;
   const int64_t rtp = (rts + 7) / 8 * 8;
   const bool hp = a_absmax != nullptr;                 // scaled two-plane mode: the image's fp16 half and its maximum
@@ -1003,23 +876,19 @@ static int proj_rows_f32(const void *A_, int64_t lda, int64_t M, int K, const vo
   const int n_cu = cu_count();
   // a multiple of 8: slot u of a workgroup keeps u % 8 (its XCD label), so "my next slot is invalid" means "nothing
   // further for me" only then (a.tiles is a multiple of 8 by construction)
-  int64_t grid = (int64_t)n_cu * (shape == 1 ? 1 : (shape == 2 && hp ? AMPCONV_PROJ_ROWS_128_WAVES : 2)) / kXcd * kXcd;
+  int64_t grid = (int64_t)n_cu * 2 / kXcd * kXcd;
   if (grid < kXcd) grid = kXcd;
   if (grid > a.tiles) grid = a.tiles;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned g = (unsigned)grid;
-#define ROWS_LAUNCH(BM_, BN_, WM_, WN_, NT_)                                                          \
-  do {                                                                                                \
-    if (out_bound) proj_rows_kernel<BM_, BN_, WM_, WN_, false, true, true><<<g, NT_, 0, st>>>(a); \
-    else if (hp && ragged) proj_rows_kernel<BM_, BN_, WM_, WN_, true, true><<<g, NT_, 0, st>>>(a);     \
-    else if (hp) proj_rows_kernel<BM_, BN_, WM_, WN_, false, true><<<g, NT_, 0, st>>>(a);              \
-    else if (ragged) proj_rows_kernel<BM_, BN_, WM_, WN_, true, false><<<g, NT_, 0, st>>>(a);          \
-    else proj_rows_kernel<BM_, BN_, WM_, WN_, false, false><<<g, NT_, 0, st>>>(a);                     \
-  } while (0)
-  if (shape == 0) ROWS_LAUNCH(128, 256, 2, 2, 256);
-  else if (shape == 1) ROWS_LAUNCH(256, 256, 2, 4, 512);
-  else ROWS_LAUNCH(128, 128, 2, 2, 256);
-#undef ROWS_LAUNCH
+  // [BN == 128][mode]: six products {whole, ragged}, scaled {whole, ragged}, scaled with plane output
+  typedef void (*Kernel)(RowsArgs);
+  static const Kernel table[2][5] = {
+      {proj_rows_kernel<128, 256, 2, 2, false, false>, proj_rows_kernel<128, 256, 2, 2, true, false>,
+       proj_rows_kernel<128, 256, 2, 2, false, true>, proj_rows_kernel<128, 256, 2, 2, true, true>,
+       proj_rows_kernel<128, 256, 2, 2, false, true, true>},
+      {proj_rows_kernel<128, 128, 2, 2, false, false>, proj_rows_kernel<128, 128, 2, 2, true, false>,
+       proj_rows_kernel<128, 128, 2, 2, false, true>, proj_rows_kernel<128, 128, 2, 2, true, true>,
+       proj_rows_kernel<128, 128, 2, 2, false, true, true>}};
+  table[bn == 128][out_bound ? 4 : 2 * hp + ragged]<<<(unsigned)grid, 256, 0, (hipStream_t)stream>>>(a);
   return ampconv_launch_status();
 }
 
@@ -1046,213 +915,11 @@ extern "C" int ampconv_proj_rows_planes(const void *A, int64_t lda, int64_t M, i
                        plane_dh, row_scale, stream);
 }
 
-// bound of the magnitudes of out = A W^T + bias from the largest magnitude of A: a_absmax * max_n sum_k |W[n][k]| +
-// max_n |bias[n]| (W[n][k] at W[n * stride_n + k * stride_k]) -- what the plane output of proj_rows scales by, known
-// BEFORE the product runs.  One workgroup: the weights are a few hundred KB.
-namespace {
-__global__ __launch_bounds__(1024) void out_bound_kernel(const float *__restrict__ W, int64_t sn, int64_t sk, int N, int K,
-                                                         const float *__restrict__ bias, const float *__restrict__ amax,
-                                                         float *__restrict__ out) {
-  __shared__ float red[2][16];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  float l1 = 0.f, bm = 0.f;
-  for (int n = w; n < N; n += 16) {
-    float sum = 0.f;
-    for (int k = lane; k < K; k += 64) sum += finite_abs(W[(int64_t)n * sn + (int64_t)k * sk]);
-    l1 = fmaxf(l1, wave_sum(sum));
-  }
-  if (bias)
-    for (int n = threadIdx.x; n < N; n += 1024) bm = fmaxf(bm, finite_abs(bias[n]));
-  bm = wave_max(bm);
-  if (lane == 0) { red[0][w] = l1; red[1][w] = bm; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int i = 1; i < 16; ++i) { l1 = fmaxf(l1, red[0][i]); bm = fmaxf(bm, red[1][i]); }
-    out[0] = *amax * l1 + bm;
-  }
-}
-}  // namespace
-
-extern "C" int ampconv_proj_out_bound(const void *W, int64_t stride_n, int64_t stride_k, int N, int K, const void *bias,
-                                      const float *a_absmax, float *out, void *stream) {
-  if (!W || !a_absmax || !out || N <= 0 || K <= 0) return AMPCONV_E_BADARG;
-  out_bound_kernel<<<1, 1024, 0, (hipStream_t)stream>>>((const float *)W, stride_n, stride_k, N, K, (const float *)bias,
-                                                        a_absmax, out);
-  return ampconv_launch_status();
-}
-
-// plane slots -> fp32, in place layout (the reverse of the PLANES epilogue; the lazily served side outputs and the
-// fall-back paths read the projection buffer as fp32): X[M, K] with K a multiple of 32, rows ld floats apart
-namespace {
-__global__ __launch_bounds__(256) void planes_to_f32_kernel(const char *__restrict__ X, int64_t ld, int64_t M, int K8, int dh,
-                                                            const float *__restrict__ bound, float *__restrict__ out,
-                                                            int64_t ldo) {
-  const float u = 1.f / plane_scale(*bound);
-  const int pps = dh / 8;                                  // 8-channel pieces per slot
-  const int64_t total = M * K8;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int64_t row = i / K8;
-    const int r = (int)(i - row * K8), slot = r / pps, c = r - slot * pps;
-    const char *src = X + (row * ld + (int64_t)slot * dh) * 4 + 16 * c;
-    const uint4 h = *reinterpret_cast<const uint4 *>(src), l = *reinterpret_cast<const uint4 *>(src + 2 * dh);
-    const unsigned hu[4] = {h.x, h.y, h.z, h.w}, lu[4] = {l.x, l.y, l.z, l.w};
-    float v[8];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const f16x2 hv = __builtin_bit_cast(f16x2, hu[k]), lv = __builtin_bit_cast(f16x2, lu[k]);
-      v[2 * k] = ((float)hv[0] + (float)lv[0]) * u;
-      v[2 * k + 1] = ((float)hv[1] + (float)lv[1]) * u;
-    }
-    float *o = out + row * ldo + slot * dh + 8 * c;
-    *reinterpret_cast<float4 *>(o) = make_float4(v[0], v[1], v[2], v[3]);
-    *reinterpret_cast<float4 *>(o + 4) = make_float4(v[4], v[5], v[6], v[7]);
-  }
-}
-}  // namespace
-
-extern "C" int ampconv_planes_to_f32(const void *X, int64_t ld, int64_t M, int K, int plane_dh, const float *bound, void *out,
-                                     int64_t ldo, void *stream) {
-  if (M < 0 || K <= 0 || (plane_dh != 32 && plane_dh != 16) || K % plane_dh || ld < K || ldo < K || ld % 4 || ldo % 4 || !bound)
-    return AMPCONV_E_BADARG;
-  if (M == 0) return AMPCONV_OK;
-  if (!X || !out || (uintptr_t)X % 16 || (uintptr_t)out % 16) return AMPCONV_E_BADARG;
-  const int64_t pieces = M * (K / 8);
-  int64_t grid = (pieces + 255) / 256;
-  const int64_t cap = (int64_t)cu_count() * 16;
-  if (grid > cap) grid = cap;
-  planes_to_f32_kernel<<<(unsigned)grid, 256, 0, (hipStream_t)stream>>>((const char *)X, ld, M, K / 8, plane_dh, bound,
-                                                                        (float *)out, ldo);
-  return ampconv_launch_status();
-}
-
-// largest finite magnitude of X[M, K] (row stride ld), merged into *out by an atomic max: zero it first (reset != 0
-// does) or let several calls accumulate.  NaN and infinities are skipped: they propagate through the products by
-// themselves, in the rows they sit in.
-namespace {
-template <typename T>
-__global__ __launch_bounds__(256) void absmax_kernel(const T *__restrict__ X, int64_t ld, int64_t M, int K4,
-                                                     float *__restrict__ out) {
-  // K4 = 16-byte pieces per row; a workgroup walks pieces blockIdx.x * 256 + t, + gridDim.x * 256, ...
-  constexpr int EPP = 16 / sizeof(T);
-  const int64_t total = M * K4;
-  float m = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int64_t row = i / K4;
-    const int c = (int)(i - row * K4);
-    const uint4 raw = *reinterpret_cast<const uint4 *>(X + row * ld + (int64_t)c * EPP);
-    if constexpr (sizeof(T) == 4) {
-      m = fmaxf(m, fmaxf(fmaxf(finite_abs(__builtin_bit_cast(float, raw.x)), finite_abs(__builtin_bit_cast(float, raw.y))),
-                         fmaxf(finite_abs(__builtin_bit_cast(float, raw.z)), finite_abs(__builtin_bit_cast(float, raw.w)))));
-    } else {
-      const unsigned u[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        m = fmaxf(m, fmaxf(finite_abs(lo_as_f32(u[k])), finite_abs(hi_as_f32(u[k]))));
-    }
-  }
-  __shared__ float red[4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    atomicMax(reinterpret_cast<unsigned *>(out), __builtin_bit_cast(unsigned, m));
-  }
-}
-}  // namespace
-
-extern "C" int ampconv_absmax(const void *X, int64_t ld, int64_t M, int K, int dtype, float *out, int reset,
-                              void *stream) {
-  if (dtype != AMPCONV_F32 && dtype != AMPCONV_BF16) return AMPCONV_E_DTYPE;
-  const int epp = dtype == AMPCONV_F32 ? 4 : 8;
-  if (!out || M < 0 || K < 0 || K % epp || ld < K || ld % epp) return AMPCONV_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
-  if (reset) {
-    const hipError_t e = hipMemsetAsync(out, 0, sizeof(float), st);
-    if (e != hipSuccess) return (int)e;
-  }
-  if (M == 0 || K == 0) return AMPCONV_OK;
-  if (!X || (uintptr_t)X % 16) return AMPCONV_E_BADARG;
-  const int64_t pieces = M * (K / epp);
-  int64_t grid = (pieces + 255) / 256;
-  const int64_t cap = (int64_t)cu_count() * 16;         // eight loads per thread and more: the atomics stay few
-  if (grid > cap) grid = cap;
-  if (dtype == AMPCONV_F32)
-    absmax_kernel<float><<<(unsigned)grid, 256, 0, st>>>((const float *)X, ld, M, K / epp, out);
-  else
-    absmax_kernel<unsigned short><<<(unsigned)grid, 256, 0, st>>>((const unsigned short *)X, ld, M, K / epp, out);
-  return ampconv_launch_status();
-}
-
-// the same pass with a RANGE statistic beside the maximum (fp32): out[0] = largest finite magnitude, out[1] = the smallest
-// non-zero maximum of any group of 8 consecutive 16-byte pieces (32 channels: one head slot of a row where K % 32 == 0).
-// out[1] far below out[0] means whole rows / heads live binades under the tensor's maximum -- the data on which ONE scale
-// per tensor costs the small rows their low plane (include/ampconv.h "SCALED MODE"); the caller then takes the exact
-// kernels.  Single elements near zero do not count (absolute error is what a sum feels), all-zero groups neither.
-namespace {
-__global__ void absmax_stats_init_kernel(float *out) {
-  out[0] = 0.f;
-  out[1] = __builtin_inff();
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_get(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true));
-}
-__global__ __launch_bounds__(256) void absmax_stats_kernel(const float *__restrict__ X, int64_t ld, int64_t M, int K4,
-                                                           float *__restrict__ out) {
-  const int64_t total = M * K4;
-  float m = 0.f, smin = __builtin_inff();
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int64_t row = i / K4;
-    const int c = (int)(i - row * K4);
-    const float4 v = *reinterpret_cast<const float4 *>(X + row * ld + (int64_t)c * 4);
-    const float m4 = finite_abs_max(0.f, v);
-    m = fmaxf(m, m4);
-    float g = fmaxf(m4, dpp_get<0xB1>(m4));     // quad_perm [1,0,3,2]
-    g = fmaxf(g, dpp_get<0x4E>(g));             // quad_perm [2,3,0,1]
-    g = fmaxf(g, dpp_get<0x141>(g));            // row_half_mirror: the 8 lanes of a half row (masked lanes read as 0)
-    if (g > 0.f) smin = fminf(smin, g);
-  }
-  __shared__ float red[2][4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    m = fmaxf(m, __shfl_xor(m, o));
-    smin = fminf(smin, __shfl_xor(smin, o));
-  }
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = m;
-    red[1][threadIdx.x >> 6] = smin;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    m = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
-    smin = fminf(fminf(red[1][0], red[1][1]), fminf(red[1][2], red[1][3]));
-    atomicMax(reinterpret_cast<unsigned *>(out), __builtin_bit_cast(unsigned, m));          // non-negative floats order
-    atomicMin(reinterpret_cast<unsigned *>(out + 1), __builtin_bit_cast(unsigned, smin));   // as their bits
-  }
-}
-}  // namespace
-
-extern "C" int ampconv_absmax_stats(const void *X, int64_t ld, int64_t M, int K, float *out, void *stream) {
-  if (!out || M < 0 || K < 0 || K % 4 || ld < K || ld % 4) return AMPCONV_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
-  absmax_stats_init_kernel<<<1, 1, 0, st>>>(out);
-  if (M == 0 || K == 0) return ampconv_launch_status();
-  if (!X || (uintptr_t)X % 16) return AMPCONV_E_BADARG;
-  const int64_t pieces = M * (K / 4);
-  int64_t grid = (pieces + 255) / 256;
-  const int64_t cap = (int64_t)cu_count() * 16;
-  if (grid > cap) grid = cap;
-  absmax_stats_kernel<<<(unsigned)grid, 256, 0, st>>>((const float *)X, ld, M, K / 4, out);
-  return ampconv_launch_status();
-}
-
 extern "C" size_t ampconv_proj_wgrad_workspace_bytes(int64_t M, int Na, int Nb, int dtype) {
   if (dtype == AMPCONV_BF16) return ampconv_proj_wgrad_workspace_bytes_bf16(M, Na, Nb);
   if (dtype != AMPCONV_F32 || M < 0 || Na <= 0 || Nb <= 0 || Na % 4 || Nb % 4) return 0;
   const int Nap = (Na + 127) / 128 * 128, Nbp = (Nb + 127) / 128 * 128;
-  const WgradPlan p = wgrad_plan(M, Nap, Nbp);
+  const WgradPlan p = wgrad_plan(M, Nap, Nbp, kRS, false);
   // [S partial slabs][one flag per row: used with a mask]
   return (size_t)p.S * ((size_t)Nap * Nbp + Nap) * sizeof(float) + ((size_t)M + 3) / 4 * 16;
 }
@@ -1284,7 +951,7 @@ extern "C" int ampconv_proj_wgrad(const void *A_, int64_t lda, const void *B_, i
     return AMPCONV_E_BADARG;
   const int Nap = (Na + 127) / 128 * 128, Nbp = (Nb + 127) / 128 * 128;
   const bool ragged = Nap != Na || Nbp != Nb;
-  const WgradPlan p = wgrad_plan(M, Nap, Nbp);
+  const WgradPlan p = wgrad_plan(M, Nap, Nbp, kRS, false);
   const size_t n_all = (size_t)Nap * Nbp + Nap;
   const size_t slab_bytes = (size_t)p.S * n_all * sizeof(float);
   if (workspace_bytes < slab_bytes + (rowptr ? ((size_t)M + 3) / 4 * 16 : 0)) return AMPCONV_E_WORKSPACE;
@@ -1298,31 +965,17 @@ extern "C" int ampconv_proj_wgrad(const void *A_, int64_t lda, const void *B_, i
   const bool hp = a_absmax != nullptr;
   const int ntiles = (Nap / p.ti) * (Nbp / p.tj);
   const unsigned grid = (unsigned)(((p.S + 7) / 8 * 8) * ntiles);
-#define WGRAD_LAUNCH(TI_, TJ_, WI_, WJ_, NT_)                                                              \
-  do {                                                                                                     \
-    if (hp) {                                                                                              \
-      if (rowptr && ragged) proj_wgrad_kernel<TI_, TJ_, WI_, WJ_, true, true, true><<<grid, NT_, 0, st>>>(a);      \
-      else if (rowptr) proj_wgrad_kernel<TI_, TJ_, WI_, WJ_, true, false, true><<<grid, NT_, 0, st>>>(a);          \
-      else if (ragged) proj_wgrad_kernel<TI_, TJ_, WI_, WJ_, false, true, true><<<grid, NT_, 0, st>>>(a);          \
-      else proj_wgrad_kernel<TI_, TJ_, WI_, WJ_, false, false, true><<<grid, NT_, 0, st>>>(a);                     \
-    } else if (rowptr && ragged) proj_wgrad_kernel<TI_, TJ_, WI_, WJ_, true, true, false><<<grid, NT_, 0, st>>>(a); \
-    else if (rowptr) proj_wgrad_kernel<TI_, TJ_, WI_, WJ_, true, false, false><<<grid, NT_, 0, st>>>(a);           \
-    else if (ragged) proj_wgrad_kernel<TI_, TJ_, WI_, WJ_, false, true, false><<<grid, NT_, 0, st>>>(a);           \
-    else proj_wgrad_kernel<TI_, TJ_, WI_, WJ_, false, false, false><<<grid, NT_, 0, st>>>(a);                      \
-  } while (0)
-  if (p.ti == 256) WGRAD_LAUNCH(256, 256, 2, 4, 512);
-  else if (p.tj == 256) WGRAD_LAUNCH(128, 256, 2, 2, 256);
-  else WGRAD_LAUNCH(128, 128, 2, 2, 256);
-#undef WGRAD_LAUNCH
+  // [tile: 256 x 256 (eight waves), 128 x 256, 128 x 128][scaled][mask][ragged]
+  typedef void (*Kernel)(WgradArgs);
+#define WGRAD_TILE(TI_, TJ_, WI_, WJ_)                                                                                       \
+  {{{proj_wgrad_kernel<TI_, TJ_, WI_, WJ_, false, false, false>, proj_wgrad_kernel<TI_, TJ_, WI_, WJ_, false, true, false>}, \
+    {proj_wgrad_kernel<TI_, TJ_, WI_, WJ_, true, false, false>, proj_wgrad_kernel<TI_, TJ_, WI_, WJ_, true, true, false>}},  \
+   {{proj_wgrad_kernel<TI_, TJ_, WI_, WJ_, false, false, true>, proj_wgrad_kernel<TI_, TJ_, WI_, WJ_, false, true, true>},   \
+    {proj_wgrad_kernel<TI_, TJ_, WI_, WJ_, true, false, true>, proj_wgrad_kernel<TI_, TJ_, WI_, WJ_, true, true, true>}}}
+  static const Kernel table[3][2][2][2] = {WGRAD_TILE(256, 256, 2, 4), WGRAD_TILE(128, 256, 2, 2), WGRAD_TILE(128, 128, 2, 2)};
+#undef WGRAD_TILE
+  table[p.ti == 256 ? 0 : (p.tj == 256 ? 1 : 2)][hp][rowptr != nullptr][ragged]<<<grid, p.ti == 256 ? 512 : 256, 0, st>>>(a);
   wgrad_reduce_kernel<<<(unsigned)((n_all / 4 + 31) / 32), 256, 0, st>>>((const float *)workspace, p.S, Na, Nb, Nap, Nbp,
-                                                                         dW, colsum, a_absmax, b_absmax);
+                                                                         ReduceF32{dW, colsum, a_absmax, b_absmax});
   return ampconv_launch_status();
 }
-
-#ifdef AMPCONV_PROJ_STAMPS
-// diagnostic build only (tools/stamp_proj.py)
-extern "C" int ampconv_debug_read_proj_stamps(unsigned long long *out, int n) {
-  if (hipDeviceSynchronize() != hipSuccess) return -1;
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_proj_stamps), sizeof(unsigned long long) * (size_t)n);
-}
-#endif

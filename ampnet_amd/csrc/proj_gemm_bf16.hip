@@ -15,7 +15,7 @@
 //
 //   proj_rows_bf16   out[M, N] = A[M, K] W^T (+ bias) (* row mask)
 //   proj_wgrad_bf16  dW[Na, Nb] = A[M, Na]^T B[M, Nb], colsum(mask * A)
-#include <stdlib.h>
+// (transposed-read fragments and their fences: plane16.h; the reduction over row slices and its plan: proj_common.h)
 #include <type_traits>
 #include "proj_common.h"
 
@@ -222,11 +222,7 @@ __global__ __launch_bounds__(256, 2) void proj_rows_bf16_kernel(RowsArgsB a) {
       for (int i = 0; i < MTW; ++i)
 #pragma unroll
         for (int j = 0; j < NTW; ++j) {
-#ifdef AMPCONV_PROJ_ABLATE_MFMA        // timing-only developer build: fragments read, nothing multiplied
-          asm volatile("" ::"v"(af[p][i]), "v"(bf[p][j]));
-#else
           acc[i][j] = MFMA32(af[p][i], bf[p][j], acc[i][j]);
-#endif
           ++c;
           if (c == NM / 4) fragments(std::integral_constant<int, 1>{});      // second half's fragments, a quarter ahead
 #pragma unroll
@@ -359,18 +355,14 @@ __global__ __launch_bounds__(256, 2) void proj_rows_bf16_kernel(RowsArgsB a) {
               const int row = sr + 16 * g;
               const float4 v0 = *reinterpret_cast<const float4 *>(stage + row * 32 + 8 * sc);
               const float4 v1 = *reinterpret_cast<const float4 *>(stage + row * 32 + 8 * sc + 4);
-              const u32x4 pk = {cvt_pk_bf16(v0.x, v0.y), cvt_pk_bf16(v0.z, v0.w), cvt_pk_bf16(v1.x, v1.y),
+              const i32x4 pk = {cvt_pk_bf16(v0.x, v0.y), cvt_pk_bf16(v0.z, v0.w), cvt_pk_bf16(v1.x, v1.y),
                                 cvt_pk_bf16(v1.z, v1.w)};
-#ifdef AMPCONV_PROJ_ABLATE_STORES      // timing-only developer build: everything but the global stores
-              asm volatile("" ::"v"(pk));
-#else
               if (GATHER) {
                 const int orow = rowtab[rl0 + row];
                 if (orow >= 0 && (!RAGGED || colt + 8 * sc < a.N))
-                  *reinterpret_cast<u32x4 *>(a.out + (int64_t)orow * a.ldc + colt + 8 * sc) = pk;
+                  *reinterpret_cast<i32x4 *>(a.out + (int64_t)orow * a.ldc + colt + 8 * sc) = pk;
               } else if ((!decltype(ragged_rows)::value || cur.row0 + rl0 + row < a.M) && (!RAGGED || colt + 8 * sc < a.N))
-                *reinterpret_cast<u32x4 *>(a.out + (cur.row0 + rl0 + row) * a.ldc + colt + 8 * sc) = pk;
-#endif
+                *reinterpret_cast<i32x4 *>(a.out + (cur.row0 + rl0 + row) * a.ldc + colt + 8 * sc) = pk;
             }
           }
         }
@@ -400,7 +392,7 @@ __global__ __launch_bounds__(256, 2) void proj_rows_bf16_kernel(RowsArgsB a) {
 // Per-row flags (1.0 / 0.0: row inside the slice AND node has an in-edge; row_flags_kernel) travel with the stage
 // (64 bytes); they act on the column sums (VALU, from the LDS image).  Rows beyond the slice and columns beyond Na /
 // Nb are fetched from a zero row.  Partial tiles per slice go to the workspace and are added in slice order
-// (bitwise reproducible, no atomics).
+// (wgrad_reduce_kernel, proj_common.h: bitwise reproducible, no atomics).
 struct WgradArgsB {
   const __bf16 *A;
   int64_t lda;
@@ -550,19 +542,14 @@ __global__ __launch_bounds__(T == 256 ? 512 : 256, 2) void proj_wgrad_bf16_kerne
         af[i] = tr_frag(r0, r0 + 4 * kRow);
       }
       // every transposed fragment of the half stage is in its registers before the first MFMA issues, and none is read in
-      // among the MFMAs (csrc/proj_gemm.hip, proj_wgrad_kernel: the schedule hipcc picks by itself gave wrong sums there)
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 7\n\ts_nop 7" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
+      // among the MFMAs (plane16.h; proj_gemm.hip, proj_wgrad_kernel: the schedule hipcc picks by itself gave wrong sums there)
+      TR_FRAG_FENCE_IDLE();
 #pragma unroll
       for (int i = 0; i < NIW; ++i)
 #pragma unroll
         for (int j = 0; j < NJW; ++j) acc[i][j] = MFMA32(af[i], bf[j], acc[i][j]);
-      // (... and the next half stage's reads do not redefine a fragment register right behind the MFMA that reads it:
-      // tools/scan_tr_hazard.py --gate, rule WAR)
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_nop 7" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
+      // (... and the next half stage's reads do not redefine a fragment register right behind the MFMA that reads it)
+      TR_WAR_GUARD();
     }
     if (do_cs) {
       const char *fl = smem + oFl + (s & (NBUF - 1)) * kMeta;
@@ -641,73 +628,6 @@ __global__ __launch_bounds__(256) void row_flags_kernel(const int32_t *__restric
                                                  f[6] | (f[7] << 16)};
 }
 
-// out[e] = bf16(sum over the slices of part[s][e]); the fp32 kernel's reduction (proj_gemm.hip) with a bf16 epilogue
-__global__ __launch_bounds__(256) void wgrad_reduce_bf16_kernel(const float *__restrict__ part, int S, int Na, int Nb,
-                                                                int Nap, int Nbp, unsigned short *__restrict__ dW,
-                                                                unsigned short *__restrict__ colsum) {
-  __shared__ float4 red[8][32];
-  const int el = threadIdx.x & 31, g = threadIdx.x >> 5;
-  const int64_t n_dw = (int64_t)Nap * Nbp, n_all = n_dw + Nap;
-  const int64_t e = ((int64_t)blockIdx.x * 32 + el) * 4;
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (e < n_all) {
-    float4 a1 = acc;
-    int s = g;
-    for (; s + 8 < S; s += 16) {
-      const float4 v0 = *reinterpret_cast<const float4 *>(part + (size_t)s * n_all + e);
-      const float4 v1 = *reinterpret_cast<const float4 *>(part + (size_t)(s + 8) * n_all + e);
-      acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
-      a1.x += v1.x; a1.y += v1.y; a1.z += v1.z; a1.w += v1.w;
-    }
-    if (s < S) {
-      const float4 v0 = *reinterpret_cast<const float4 *>(part + (size_t)s * n_all + e);
-      acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
-    }
-    acc.x += a1.x; acc.y += a1.y; acc.z += a1.z; acc.w += a1.w;
-  }
-  red[g][el] = acc;
-  __syncthreads();
-  if (g == 0 && e < n_all) {
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-      const float4 v = red[k][el];
-      acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-    }
-    const i32x2 pk = {(int)cvt_pk_bf16(acc.x, acc.y), (int)cvt_pk_bf16(acc.z, acc.w)};
-    if (e < n_dw) {
-      const int i = (int)(e / Nbp), j = (int)(e - (int64_t)i * Nbp);
-      if (i < Na && j < Nb) *reinterpret_cast<i32x2 *>(dW + (size_t)i * Nb + j) = pk;
-    } else if (colsum && e - n_dw < Na) {
-      *reinterpret_cast<i32x2 *>(colsum + (e - n_dw)) = pk;
-    }
-  }
-}
-
-struct WgradPlanB {
-  int S;
-  int64_t rows_per_slice;
-  int T;
-};
-inline WgradPlanB wgrad_plan_bf16(int64_t M, int Nap, int Nbp) {       // padded shape (multiples of 128)
-  WgradPlanB p;
-  static const bool small_t = [] {                        // developer switch: 128 x 128 tiles of four waves, two per CU
-    const char *e = getenv("AMPCONV_PROJ_WGRAD_BF16_T");
-    return e && atoi(e) == 128;
-  }();
-  p.T = (Nap % 256 == 0 && Nbp % 256 == 0 && !small_t) ? 256 : 128;
-  const int64_t ntiles = (int64_t)(Nap / p.T) * (Nbp / p.T);
-  const int64_t nstages = (M + kRSB - 1) / kRSB;
-  // one round of workgroups: slices are dealt to the 8 XCDs in turn and every slice brings `ntiles` workgroups, so
-  // an XCD's 32 CUs (x 2 for the 4-wave shape) hold floor(32 / ntiles) slices each (proj_gemm.hip: wgrad_plan)
-  const int per_xcd = (p.T == 256 ? 1 : 2) * 32;
-  int64_t S = (int64_t)kXcd * (per_xcd / ntiles > 0 ? per_xcd / ntiles : 1);
-  if (S > nstages) S = nstages > 0 ? nstages : 1;
-  p.rows_per_slice = ((nstages + S - 1) / S) * kRSB;
-  p.S = (int)((M + p.rows_per_slice - 1) / p.rows_per_slice);
-  if (p.S < 1) p.S = 1;
-  return p;
-}
-
 inline size_t align16(size_t x) { return (x + 15) / 16 * 16; }
 
 }  // namespace
@@ -757,17 +677,13 @@ int ampconv_proj_rows_bf16(const void *A, int64_t lda, int64_t M, int K, const v
   int64_t grid = (int64_t)cu_count() * 2 / kXcd * kXcd;
   if (grid < kXcd) grid = kXcd;
   if (grid > a.tiles) grid = a.tiles;
-  const unsigned g = (unsigned)grid;
-#define ROWS_LAUNCH(BN_, RG_)                                                                    \
-  do {                                                                                           \
-    if (nodes) proj_rows_bf16_kernel<BN_, RG_, true><<<g, 256, 0, stream>>>(a);                  \
-    else proj_rows_bf16_kernel<BN_, RG_, false><<<g, 256, 0, stream>>>(a);                       \
-  } while (0)
-  if (bn == 256 && !ragged) ROWS_LAUNCH(256, false);
-  else if (bn == 256) ROWS_LAUNCH(256, true);
-  else if (!ragged) ROWS_LAUNCH(128, false);
-  else ROWS_LAUNCH(128, true);
-#undef ROWS_LAUNCH
+  typedef void (*Kernel)(RowsArgsB);
+  static const Kernel table[2][2][2] = {      // [BN == 128][ragged][node list]
+      {{proj_rows_bf16_kernel<256, false, false>, proj_rows_bf16_kernel<256, false, true>},
+       {proj_rows_bf16_kernel<256, true, false>, proj_rows_bf16_kernel<256, true, true>}},
+      {{proj_rows_bf16_kernel<128, false, false>, proj_rows_bf16_kernel<128, false, true>},
+       {proj_rows_bf16_kernel<128, true, false>, proj_rows_bf16_kernel<128, true, true>}}};
+  table[bn == 128][ragged][nodes != nullptr]<<<(unsigned)grid, 256, 0, stream>>>(a);
   return ampconv_launch_status();
 }
 
@@ -776,7 +692,7 @@ int ampconv_proj_rows_bf16(const void *A, int64_t lda, int64_t M, int K, const v
 size_t ampconv_proj_wgrad_workspace_bytes_bf16(int64_t M, int Na, int Nb) {
   if (M < 0 || Na <= 0 || Nb <= 0 || Na % 8 || Nb % 8) return 0;
   const int Nap = (Na + 127) / 128 * 128, Nbp = (Nb + 127) / 128 * 128;
-  const WgradPlanB p = wgrad_plan_bf16(M, Nap, Nbp);
+  const WgradPlan p = wgrad_plan(M, Nap, Nbp, kRSB, true);
   // [partials][zero row 512 B][flags + 256 B][row map: (rows + 6 stages) int32, node lists only: sized always]
   const size_t rows = (size_t)p.S * p.rows_per_slice;
   return (size_t)p.S * ((size_t)Nap * Nbp + Nap) * sizeof(float) + 512 + align16(rows * 2) + 256 + (rows + 6 * 32) * 4;
@@ -799,7 +715,7 @@ int ampconv_proj_wgrad_bf16(const void *A, int64_t lda, const void *B, int64_t l
   if (!A || !B || (uintptr_t)A % 16 || (uintptr_t)B % 16 || !workspace || (uintptr_t)workspace % 16)
     return AMPCONV_E_BADARG;
   const int Nap = (Na + 127) / 128 * 128, Nbp = (Nb + 127) / 128 * 128;
-  const WgradPlanB p = wgrad_plan_bf16(Me, Nap, Nbp);
+  const WgradPlan p = wgrad_plan(Me, Nap, Nbp, kRSB, true);
   const size_t n_all = (size_t)Nap * Nbp + Nap;
   const size_t part_bytes = (size_t)p.S * n_all * sizeof(float);
   const int64_t Mpad = (int64_t)p.S * p.rows_per_slice;
@@ -813,13 +729,14 @@ int ampconv_proj_wgrad_bf16(const void *A, int64_t lda, const void *B, int64_t l
                                                                                  nodes, rowmap);
   WgradArgsB a{(const __bf16 *)A, lda, (const __bf16 *)B, ldb, Me, Na, Nb, (float *)workspace, p.S, p.rows_per_slice,
                Nap, Nbp, (const __bf16 *)flags, (const __bf16 *)zrow, colsum ? 1 : 0, rowmap};
-  const int ntiles = (Nap / p.T) * (Nbp / p.T);
+  const int ntiles = (Nap / p.ti) * (Nbp / p.tj);
   const unsigned grid = (unsigned)(((p.S + 7) / 8 * 8) * ntiles);
-  if (p.T == 256 && nodes) proj_wgrad_bf16_kernel<256, true><<<grid, 512, 0, st>>>(a);
-  else if (p.T == 256) proj_wgrad_bf16_kernel<256, false><<<grid, 512, 0, st>>>(a);
-  else if (nodes) proj_wgrad_bf16_kernel<128, true><<<grid, 256, 0, st>>>(a);
-  else proj_wgrad_bf16_kernel<128, false><<<grid, 256, 0, st>>>(a);
-  wgrad_reduce_bf16_kernel<<<(unsigned)((n_all / 4 + 31) / 32), 256, 0, st>>>(
-      (const float *)workspace, p.S, Na, Nb, Nap, Nbp, (unsigned short *)dW, (unsigned short *)colsum);
+  typedef void (*Kernel)(WgradArgsB);
+  static const Kernel table[2][2] = {      // [T == 128][node list]
+      {proj_wgrad_bf16_kernel<256, false>, proj_wgrad_bf16_kernel<256, true>},
+      {proj_wgrad_bf16_kernel<128, false>, proj_wgrad_bf16_kernel<128, true>}};
+  table[p.ti == 128][nodes != nullptr]<<<grid, p.ti == 256 ? 512 : 256, 0, st>>>(a);
+  wgrad_reduce_kernel<<<(unsigned)((n_all / 4 + 31) / 32), 256, 0, st>>>(
+      (const float *)workspace, p.S, Na, Nb, Nap, Nbp, ReduceBf16{(unsigned short *)dW, (unsigned short *)colsum});
   return ampconv_launch_status();
 }

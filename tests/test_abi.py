@@ -242,7 +242,7 @@ def test_register_budgets_of_the_kernels_that_must_not_spill():
     for f in files:
         usage.update(json.load(open(f)))
     rows = {k: v for k, v in usage.items() if 'proj_rows_kernel' in k and 'bf16' not in k}
-    assert len(rows) == 15              # 3 tile shapes x (ragged x {six products, scaled} + plane output)
+    assert len(rows) == 10              # 2 tile shapes x (ragged x {six products, scaled} + plane output)
     for k, v in rows.items():
         ragged_six = 'ELb1ELb0ELb0EEEv' in k                  # <..., RAGGED = true, HP = false, PLANES = false>
         assert ragged_six or v['spill'] == 0, (k, v)          # (ragged six-product: compiler-managed loads, spills are safe)

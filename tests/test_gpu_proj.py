@@ -85,7 +85,9 @@ def test_proj_rows_mask_gives_exact_zero_rows(L, empty):
 @pytest.mark.parametrize('M,Na,Nb', [(37, 128, 128), (20 * 271, 384, 128), (5000, 768, 256), (70001, 256, 256),
                                      (40 * 77, 300, 100), (4000, 100, 100), (999, 192, 64), (61, 24, 8), (20 * 40, 200, 100),
                                      # several stages per row slice (the rows of two stages are in flight), with the mask
-                                     (20 * 3000, 128, 128), (20 * 9000, 256, 256), (20 * 5000, 384, 256)])
+                                     (20 * 3000, 128, 128), (20 * 9000, 256, 256), (20 * 5000, 384, 256),
+                                     # ragged columns under the 256 x 256 and the 128 x 256 tile
+                                     (20 * 40, 200, 200), (20 * 40, 300, 200)])
 @pytest.mark.parametrize('masked', [False, True])
 def test_proj_wgrad_matches_fp64(M, Na, Nb, masked):
     from ampnet_amd.conv import functional as F_
@@ -209,7 +211,8 @@ def test_unsupported_shapes_are_refused_not_miscomputed():
 
 # ---- fp32 storage, scaled two-plane mode (include/ampconv.h "SCALED MODE"): same bar as the six-product kernels
 @pytest.mark.parametrize('M,K,N', [(5, 128, 128), (1000, 256, 768), (4096, 768, 256), (20 * 333, 256, 256),
-                                   (777, 384, 128), (260, 100, 300), (333, 100, 100), (37, 4, 12)])
+                                   (777, 384, 128), (260, 100, 300), (333, 100, 100), (37, 4, 12),
+                                   (260, 64, 192)])      # ragged N under the 256-column tile
 @pytest.mark.parametrize('magnitude', [1.0, 3e-7, 2e4])
 def test_proj_rows_scaled_matches_fp64(M, K, N, magnitude):
     from ampnet_amd.conv import functional as F_
@@ -261,7 +264,9 @@ def test_proj_rows_scaled_wide_range_rows_and_nonfinite():
 
 @pytest.mark.parametrize('M,Na,Nb', [(37, 128, 128), (20 * 271, 384, 128), (5000, 768, 256), (70001, 256, 256),
                                      (999, 100, 100), (20 * 40, 300, 100), (20 * 3000, 128, 128), (20 * 9000, 256, 256),
-                                     (20 * 5000, 384, 256)])
+                                     (20 * 5000, 384, 256),
+                                     # ragged columns under the 256 x 256 and the 128 x 256 tile
+                                     (20 * 40, 200, 200), (20 * 40, 300, 200)])
 @pytest.mark.parametrize('masked', [False, True])
 def test_proj_wgrad_scaled_matches_fp64(M, Na, Nb, masked):
     from ampnet_amd.conv import functional as F_
@@ -532,7 +537,8 @@ def test_active_nodes_lists(N, E, n_silent):
 
 
 @pytest.mark.parametrize('L', [16, 20, 33, 64, 128])
-@pytest.mark.parametrize('K,N', [(256, 768), (768, 256), (256, 256), (72, 40)])
+@pytest.mark.parametrize('K,N', [(256, 768), (768, 256), (256, 256), (72, 40),
+                                 (128, 384), (72, 200)])      # whole 128-column tiles; ragged under the 256-column tile
 def test_proj_rows_bf16_node_list(L, K, N):
     """Listed nodes: bitwise the rows of the full product; every other row of `out` untouched."""
     from ampnet_amd.conv import functional as F_
