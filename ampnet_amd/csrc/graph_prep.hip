@@ -314,11 +314,14 @@ extern "C" int ampconv_graph_build(const int64_t *edge_index, int64_t E, int64_t
   hipStream_t stream = (hipStream_t)stream_;
   const bool plans = chunk > 0 && plan_dst && plan_src;
   static const bool no_small = !env_switch("AMPCONV_CSR_SMALL", true);
-  if (!status) return AMPCONV_E_BADARG;
+  const bool small = !no_small && E > 0 && E <= kSmallMaxE && N > 0 && N <= kSmallMaxN;
+  // everything either path refuses, BEFORE the status words are zeroed: a refused call has written nothing
+  if (!status || N <= 0 || E < 0 || N > INT32_MAX || E >= INT32_MAX || !rowptr || !cscptr) return AMPCONV_E_BADARG;
+  if (E > 0 && (!edge_index || !col || !eperm || !crow || !cperm || (!small && !workspace))) return AMPCONV_E_BADARG;
+  if (E > 0 && !small && workspace_bytes < ampconv_csr_workspace_bytes(N, E)) return AMPCONV_E_WORKSPACE;
   hipError_t err = hipMemsetAsync(status, 0, 4 * sizeof(int32_t), stream);
   if (err != hipSuccess) return (int)err;
-  if (!no_small && E > 0 && E <= kSmallMaxE && N > 0 && N <= kSmallMaxN) {
-    if (!edge_index || !rowptr || !col || !eperm || !cscptr || !crow || !cperm) return AMPCONV_E_BADARG;
+  if (small) {
     SmallArgs a{edge_index, (int)E, (int)N, bits_for(N), chunk, plans ? (int)ampconv_hub_max_chunks(E, chunk) : 0,
                 {rowptr, cscptr}, {col, crow}, {eperm, cperm}, cinv, status,
                 {plans ? (int32_t *)plan_dst : nullptr, plans ? (int32_t *)plan_src : nullptr}, by_edge};

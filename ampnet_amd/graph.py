@@ -75,6 +75,8 @@ class EdgeCSR:
             bad = 0
             if plans[0] is not None or (validate and E > 0):
                 bad, self.hub_dst_chunks, self.hub_src_chunks, _ = status.tolist()
+                # (views of the header and the descriptors in use: the list of first-chunk slots the combine pass reads,
+                # at header[3], lives behind the slice in the same storage -- only the pointer of these views is used)
                 if self.hub_dst_chunks:
                     self.hub_dst = plans[0][: 4 + 4 * self.hub_dst_chunks]
                 if self.hub_src_chunks:

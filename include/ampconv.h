@@ -83,7 +83,11 @@ const char *ampconv_error_string(int code);
  *                   cinv[E] = 1 / in-degree(crow[p]) (the weight of edge p in its
  *                   destination's mean, read sequentially by the source pass)
  * `oob` (device int32) is set non-zero if any index is outside [0, N); such
- * indices are clamped so that no kernel faults.  */
+ * indices are clamped on their int64 value -- v < 0 -> 0, v >= N -> N - 1 -- and every
+ * array then describes the CLAMPED graph: col and crow lie in [0, N), eperm and cperm are
+ * permutations of the edge ids, both pointers end at E, so that no kernel that walks them
+ * faults.  E = 0 writes the flag (0) and both pointer arrays (all zero) and nothing else.
+ * A refused call (AMPCONV_E_BADARG, AMPCONV_E_WORKSPACE) has launched and written nothing.  */
 size_t ampconv_csr_workspace_bytes(int64_t N, int64_t E);
 int ampconv_csr_build(const int64_t *edge_index, int64_t E, int64_t N,
                       int32_t *rowptr, int32_t *col, int32_t *eperm,
@@ -96,7 +100,9 @@ int ampconv_csr_build(const int64_t *edge_index, int64_t E, int64_t N,
  * (two workgroups, the stable sorts in LDS); larger ones by the calls above.  Same outputs either way.
  * `status` (device int32[4]) = {bounds flag as `oob` above, chunks of plan_dst, chunks of plan_src, 0}: everything the
  * host needs back, in one 16-byte read.  `by_edge` (E int32, may be NULL): CSC position of every ORIGINAL edge id,
- * from which ampconv_csc_positions_from derives `spos` (below) in one launch.  */
+ * from which ampconv_csc_positions_from derives `spos` (below) in one launch.  `cinv` may be NULL too.  E = 0 writes
+ * the four status words (0) and both pointer arrays (all zero) and nothing else; a refused call has written nothing,
+ * the status words included.  */
 int ampconv_graph_build(const int64_t *edge_index, int64_t E, int64_t N,
                         int32_t *rowptr, int32_t *col, int32_t *eperm,
                         int32_t *cscptr, int32_t *crow, int32_t *cperm, float *cinv,
@@ -125,8 +131,17 @@ int ampconv_active_nodes(const int32_t *rowptr, const int32_t *cscptr, int64_t N
  * One wavefront per (row, head) runs as long as its longest segment.  A plan cuts every CSR
  * (or CSC) segment longer than `chunk` edges into chunks; the edge kernels then reduce each
  * chunk in its own wavefront into a partial tile in `hub_ws` and an ordered pass adds a row's
- * partial tiles (fixed order: bitwise reproducible).  plan = int32 header {n_chunks, chunk, 0, 0}
- * followed by 16-byte descriptors; the caller reads header[0] back once (n_chunks), sizes
+ * partial tiles (fixed order: bitwise reproducible).  plan = int32 header {n_chunks, chunk,
+ * n_long = long rows, offset of the row list in int32 units}, then max_chunks = 2 * (E / chunk) + 2 slots of
+ * 16-byte descriptors {row, begin, end, nfirst} (the first n_chunks in use; nfirst = the row's
+ * chunk count in its first chunk, 0 in the others), then, at the offset 4 + 4 * max_chunks, the
+ * list of the slots of the long rows' first chunks (max_chunks / 2 + 2 entries, the first n_long
+ * in use), which the ordered pass launches over.  A row's chunks occupy CONSECUTIVE slots from
+ * its first, in order k = 0, 1, ...: the partial tile of chunk k of the row whose first slot is c
+ * is tile c + k of hub_ws.  Which row takes which slots, and the order of the list, are
+ * arbitrary; no result depends on them.  ampconv_hub_plan_bytes covers all of it (header,
+ * max_chunks slots, list; 0 for chunk <= 0), and nothing behind the slots and list entries in use
+ * is written.  The caller reads header[0] back once (n_chunks), sizes
  * hub_ws with ampconv_hub_workspace_bytes and passes both to the edge calls (plan = NULL or
  * n_chunks = 0: no splitting).  n_tiles = 1 (forward, dst pass) or 2 (src pass: dK and dV).
  * A plan passed to an edge call must have been built over EXACTLY the rows the call covers --
