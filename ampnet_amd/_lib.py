@@ -6,6 +6,8 @@ export a symbol, importing/using the HIP path raises.
 import ctypes
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('AMPCONV_LIB_PATH', os.path.join(_HERE, 'libampconv.so'))   # override: dev A/B builds
 
@@ -13,6 +15,7 @@ EXPECTED_ABI = 111          # AMPCONV_VERSION of include/ampconv.h this binding 
 
 AMPCONV_F32 = 0
 AMPCONV_BF16 = 1
+DTYPES = {torch.float32: AMPCONV_F32, torch.bfloat16: AMPCONV_BF16}     # storage dtype -> the C ABI's code of it
 PASS_FWD, PASS_DST, PASS_SRC = 0, 1, 2                                        # AMPCONV_PASS_*
 FAMILY_BF16_MFMA, FAMILY_SMALL, FAMILY_MFMA, FAMILY_BLOCK, FAMILY_GENERIC = range(5)     # AMPCONV_FAMILY_*
 HUB_CHUNK = int(os.environ.get('AMPCONV_HUB_CHUNK', 0))    # edges per chunk of a long CSR/CSC segment (include/ampconv.h, long segments); 0 = by size
@@ -30,6 +33,11 @@ class View(ctypes.Structure):
     """ampconv_view_t: element (n, l, h, c) at ptr + n*node + l*row + h*head + c."""
     _fields_ = [('ptr', ctypes.c_void_p), ('node_stride', ctypes.c_int64),
                 ('row_stride', ctypes.c_int64), ('head_stride', ctypes.c_int64)]
+
+
+def ptr(t):
+    """Device address of a tensor for a void * argument; None (an optional argument left out) -> NULL."""
+    return t.data_ptr() if t is not None else None
 
 
 _vp, _i64, _i32, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_size_t

@@ -211,12 +211,8 @@ class AMPConv(MessagePassing):
             q_buf = q_buf.float()
             kv_buf = None if kv_buf is None else kv_buf.float()
             self._attn_ctx = (q_buf, kv_buf, edge_index, L, shared)
-        D, dh = self.embed_dim, self.embed_dim // self.num_heads
-        if shared:
-            Qv, Kv, Vv = (F_._view(q_buf, i * D, L, dh) for i in range(3))
-        else:
-            Qv, Kv, Vv = F_._view(q_buf, 0, L, dh), F_._view(kv_buf, 0, L, dh), F_._view(kv_buf, D, L, dh)
-        return Qv, Kv, Vv, edge_index, L
+        D = self.embed_dim
+        return *F_._qkv_views(q_buf, kv_buf, L, D, D // self.num_heads), edge_index, L
 
     @property
     def attn_output_weights(self):

@@ -1,5 +1,7 @@
 """Fused AMPConv forward/backward on MI355X: projections as dense GEMMs on the
-per-NODE rows, edge phase in hand-written HIP through the C ABI.
+per-NODE rows (projection.py: one Projections object per call, libampconv's kernels or library GEMMs), edge phase in
+hand-written HIP through the C ABI.  AMPConvFunction reads: plan -> scalars -> in-projection -> edge_fwd ->
+out-projection; out-projection backward -> edge_bwd_dst / edge_bwd_src -> in-projection backward.
 
 What it replaces in the reference (paths relative to /root/reference):
   src/ampnet/conv/amp_conv.py:24-26,28-51   propagate -> message -> mean
@@ -13,16 +15,16 @@ Data layout in HBM (fp32):
   dQKV  [N*L, 3D]   written by the two backward edge passes, consumed by one GEMM each
                     for dX and d(in_proj_weight)
 """
-import contextlib
-import ctypes
 import dataclasses
 import os
-import threading
 
 import torch
 
 from .. import _lib
+from .._lib import ptr as _ptr
 from ..graph import EdgeCSR, _stream
+from .projection import (Projections, _aligned, _tn_matmul, gemm_precision, mask_rows, masked_colsum,  # noqa: F401
+                         proj_image, proj_images, proj_native, proj_rows, proj_wgrad)
 
 
 def _view(buf2d, col_off, L, dh):
@@ -32,76 +34,10 @@ def _view(buf2d, col_off, L, dh):
     return _lib.View(buf2d.data_ptr() + buf2d.element_size() * col_off, L * W, W, dh)
 
 
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
-GEMM_PRECISIONS = ('native', 'fp32', 'bf16x3')
 # hand the softmax statistics of the destination pass to the source pass (AMPCONV_SOFTMAX_STATS=0:
 # both passes reduce their own; used by the tests to cross-check the two ways)
 SOFTMAX_STATS = os.environ.get('AMPCONV_SOFTMAX_STATS', '1') != '0'
-
-
-_GEMM_SWITCH_LOCK = threading.RLock()
-
-
-@contextlib.contextmanager
-def gemm_precision(mode):
-    """How the dense fp32 projections run.  'fp32': plain fp32 MFMA GEMMs (rocBLAS, ~135-150
-    TFLOP/s on MI355X).  'bf16x3': hipBLASLt's fp32 GEMM that splits each operand into two bf16
-    planes and sums three bf16 MFMA products in fp32 (what ROCm serves as "TF32" on gfx950, which
-    has no xf32 matrix instruction): ~2x the rate, element error ~5e-6 of the largest output
-    instead of ~6e-7 (tools/bench_gemm.py).  Inputs, outputs and accumulation stay fp32; the
-    edge kernels are not affected.
-
-    torch's switches (allow_tf32, preferred BLAS library, HIPBLASLT_ALLOW_TF32) are PROCESS-GLOBAL:
-    they are set for the duration of the block and restored, under a lock so that two layers (the
-    autograd thread runs backward) never interleave their set/restore.  fp32 GEMMs issued by OTHER
-    threads while a 'bf16x3' block is open run in that mode too -- keep the default 'fp32' if that
-    matters (tests/test_gpu_parity.py::test_gemm_precision_is_restored pins the restore)."""
-    if mode not in GEMM_PRECISIONS:
-        raise ValueError(f'gemm precision must be one of {GEMM_PRECISIONS}, got {mode!r}')
-    if mode in ('fp32', 'native'):      # 'native': libampconv's own projection kernels (proj_* below); what they
-        yield                           # do not serve (bf16 storage, D % 4 != 0) runs as plain library GEMMs
-        return
-    with _GEMM_SWITCH_LOCK:
-        prev_env = os.environ.get('HIPBLASLT_ALLOW_TF32')
-        prev_tf32 = torch.backends.cuda.matmul.allow_tf32
-        prev_lib = torch.backends.cuda.preferred_blas_library()
-        os.environ['HIPBLASLT_ALLOW_TF32'] = '1'
-        torch.backends.cuda.matmul.allow_tf32 = True
-        torch.backends.cuda.preferred_blas_library('hipblaslt')
-        try:
-            yield
-        finally:
-            torch.backends.cuda.preferred_blas_library(prev_lib)
-            torch.backends.cuda.matmul.allow_tf32 = prev_tf32
-            if prev_env is None:
-                os.environ.pop('HIPBLASLT_ALLOW_TF32', None)
-            else:
-                os.environ['HIPBLASLT_ALLOW_TF32'] = prev_env
-
-
-def _tn_matmul(a, b, chunks=128):
-    """a^T @ b for tall operands a [M, p], b [M, q] (the weight-gradient GEMMs, reduction over
-    the N*L node-token rows).  rocBLAS runs the single [p, M] x [M, q] product at 65-95 TFLOP/s
-    at M = 2e7; splitting the reduction into `chunks` batched GEMMs + one sum runs at
-    ~150 TFLOP/s (measured on MI355X, tools/bench_dw.py) and sums pairwise, i.e. more accurately."""
-    M = a.size(0)
-    if M < (1 << 18):
-        return a.t().mm(b)
-    per = M // chunks
-    main = per * chunks
-    out = torch.bmm(a[:main].view(chunks, per, -1).transpose(1, 2), b[:main].view(chunks, per, -1)).sum(0)
-    if main < M:
-        out += a[main:].t().mm(b[main:])
-    return out
-
-
-# ---- the per-node projections in libampconv.so.  fp32 storage (csrc/proj_gemm.hip): operands scaled by a power of two
-# and split into two fp16 planes, three partial products on v_mfma_f32_32x32x16_f16 (large operands; PROJ_SCALED below), or
-# split exactly into three bf16 terms, six partial products on v_mfma_f32_32x32x16_bf16; fp32 accumulate.  bf16 storage
-# (csrc/proj_gemm_bf16.hip): one product, fp32 accumulate, one rounding on the way out
+# ---- the switches of the per-node projections (projection.py; their kernels: csrc/proj_gemm.hip, csrc/proj_gemm_bf16.hip)
 NODE_LISTS = os.environ.get('AMPCONV_NODE_LISTS', '1') != '0'      # developer switch (A/B measurements)
 # fp32 storage: two scaled fp16 planes, three products (include/ampconv.h "SCALED MODE"); '0': three bf16 planes, six
 PROJ_SCALED = os.environ.get('AMPCONV_PROJ_SCALED', '1') != '0'
@@ -197,112 +133,9 @@ def absmax(t2, out=None, reset=False):
     t2 = _aligned(t2)
     if out is None:
         out, reset = torch.empty(1, dtype=torch.float32, device=t2.device), True
-    _lib.check(lib.ampconv_absmax(t2.data_ptr(), t2.stride(0), t2.size(0), t2.size(1), _code(t2.dtype), out.data_ptr(),
+    _lib.check(lib.ampconv_absmax(t2.data_ptr(), t2.stride(0), t2.size(0), t2.size(1), _lib.DTYPES[t2.dtype], out.data_ptr(),
                                   1 if reset else 0, _stream()), 'ampconv_absmax')
     return out
-
-
-def _zero(scalar):
-    """Zero a one-element fp32 device tensor on the current stream (the receiving end of proj_rows' out_amax)."""
-    _lib.check(_lib.load().ampconv_absmax(None, 0, 0, 0, _lib.AMPCONV_F32, scalar.data_ptr(), 1, _stream()),
-               'ampconv_absmax')
-
-
-def _code(dtype):
-    return _lib.AMPCONV_BF16 if dtype == torch.bfloat16 else _lib.AMPCONV_F32
-
-
-def proj_native(gemm, dtype, D):
-    """Does the 'native' mode serve this layer?  fp32 storage with embed_dim a multiple of 4, bf16 storage with a
-    multiple of 8 (rows move in 16-byte pieces)."""
-    return (gemm == 'native' and dtype in (torch.float32, torch.bfloat16)
-            and bool(_lib.load().ampconv_proj_supported(D, D, _code(dtype))))
-
-
-def _aligned(t):
-    """Rows in 16-byte pieces: a view whose first element is not 16-byte aligned (a slice of a larger tensor) is copied."""
-    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
-
-
-def proj_images(jobs):
-    """MFMA-fragment images of weights, ALL in one launch: `jobs` = [(W, transpose), ...] (at most 8), W [R, C]
-    with contiguous rows, all of one dtype; an image of W itself serves out = in @ W^T (the forward direction of
-    nn.Linear), of W^T serves out = in @ W (its input gradient).  Returns [(image bytes, N, K, dtype), ...]."""
-    lib = _lib.load()
-    descs, outs, off = (_lib.WeightImage * len(jobs))(), [], 0
-    dims = []
-    wdt = jobs[0][0].dtype
-    code = _code(wdt)
-    for W, transpose in jobs:
-        assert W.dim() == 2 and W.stride(1) == 1 and W.dtype == wdt
-        R, C = W.shape
-        N, K = (C, R) if transpose else (R, C)
-        dims.append((N, K, lib.ampconv_proj_weight_image_bytes(N, K, code)))
-    buf = torch.empty(sum(d[2] for d in dims), dtype=torch.uint8, device=jobs[0][0].device)
-    for i, ((W, transpose), (N, K, nb)) in enumerate(zip(jobs, dims)):
-        sn, sk = (1, W.stride(0)) if transpose else (W.stride(0), 1)
-        img = buf[off:off + nb]
-        descs[i] = _lib.WeightImage(W.data_ptr(), sn, sk, N, K, img.data_ptr())
-        outs.append((img, N, K, wdt))
-        off += nb
-    _lib.check(lib.ampconv_proj_weight_images(len(jobs), ctypes.cast(descs, ctypes.c_void_p), code, _stream()),
-               'ampconv_proj_weight_images')
-    return outs
-
-
-def proj_image(W, transpose=False):
-    return proj_images([(W, transpose)])[0]
-
-
-def proj_rows(a2, image, bias=None, rowptr=None, L=0, nodes=None, out=None, amax=None, out_amax=None):
-    """out[M, N] = (a2[M, K] @ B^T + bias) * [node of the row has an in-edge]  (mask only with rowptr).
-    nodes = (ids, count[, ptr]) (EdgeCSR.active_nodes): only the L rows of each listed node are computed and written
-    (bf16; the other rows of `out` keep what they hold: uninitialised unless the caller passes `out`).
-    amax (fp32 storage): one-element tensor, the operand's largest finite magnitude or a bound of it (absmax) -> the
-    two-plane scaled kernels; out_amax: a zeroed one-element tensor that receives the output's."""
-    lib = _lib.load()
-    img, N, K, wdt = image
-    assert a2.dim() == 2 and a2.size(1) == K and a2.stride(1) == 1 and a2.dtype == wdt
-    assert bias is None or bias.dtype == wdt
-    a2 = _aligned(a2)
-    if out is None:
-        out = torch.empty(a2.size(0), N, dtype=wdt, device=a2.device)
-    assert out.shape == (a2.size(0), N) and out.stride(1) == 1 and out.dtype == wdt
-    ids, cnt = (nodes[0].data_ptr(), nodes[1]) if nodes is not None else (None, 0)
-    _lib.check(lib.ampconv_proj_rows(a2.data_ptr(), a2.stride(0), a2.size(0), K, img.data_ptr(), N, _ptr(bias),
-                                     _ptr(rowptr), L, out.data_ptr(), out.stride(0), ids, cnt, _ptr(amax), _ptr(out_amax),
-                                     _code(wdt), _stream()), 'ampconv_proj_rows')
-    return out
-
-
-def proj_wgrad(a2, b2, dw, colsum=None, rowptr=None, L=0, nodes=None, amax=None):
-    """dw[Na, Nb] = (mask * a2)^T @ b2 and colsum[Na] = column sums of mask * a2, into caller-owned (views of)
-    contiguous tensors of the inputs' dtype; reduction over the rows in fixed slices (bitwise reproducible).
-    bf16: the mask acts on the column sums only (include/ampconv.h).  nodes: the sums run over the L rows of each
-    listed node only (bf16).  amax = (a2's, b2's) largest finite magnitudes (fp32 storage: scaled two-plane kernels)."""
-    lib = _lib.load()
-    M, Na = a2.shape
-    Nb = b2.size(1)
-    assert b2.size(0) == M and dw.shape == (Na, Nb) and dw.is_contiguous() and a2.stride(1) == 1 and b2.stride(1) == 1
-    assert a2.dtype == b2.dtype == dw.dtype and (colsum is None or colsum.dtype == a2.dtype)
-    a2, b2 = _aligned(a2), _aligned(b2)
-    code = _code(a2.dtype)
-    ids, cnt = (nodes[0].data_ptr(), nodes[1]) if nodes is not None else (None, 0)
-    nws = lib.ampconv_proj_wgrad_workspace_bytes(cnt * L if nodes is not None else M, Na, Nb, code)
-    ws = torch.empty(max(nws, 16) // 4, dtype=torch.float32, device=a2.device)
-    _lib.check(lib.ampconv_proj_wgrad(a2.data_ptr(), a2.stride(0), b2.data_ptr(), b2.stride(0), M, Na, Nb,
-                                      _ptr(rowptr), L, dw.data_ptr(), _ptr(colsum), ws.data_ptr(), nws, ids, cnt,
-                                      _ptr(amax[0]) if amax else None, _ptr(amax[1]) if amax else None, code,
-                                      _stream()), 'ampconv_proj_wgrad')
-
-
-def _zero_unlisted(t2, nodes, n_nodes, L):
-    """Zero the rows of the nodes a list leaves out (its CSR-shaped `ptr`: include/ampconv.h, ampconv_active_nodes)."""
-    lib = _lib.load()
-    assert t2.is_contiguous()
-    io = _lib.AMPCONV_BF16 if t2.dtype == torch.bfloat16 else _lib.AMPCONV_F32
-    _lib.check(lib.ampconv_mask_rows(t2.data_ptr(), nodes[2].data_ptr(), n_nodes, L * t2.size(1), io, _stream()),
-               'ampconv_mask_rows')
 
 
 def edge_forward(Q, K, V, csr, n_rows, L, D, H, out2d, qidx=None, dtype=_lib.AMPCONV_F32):
@@ -492,7 +325,6 @@ class AMPConvFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xq, xkv, w_in, b_in, w_out, b_out, csr, num_heads, shared, dtype=_lib.AMPCONV_F32,
                 gemm='fp32'):
-        lib = _lib.load()
         D = w_out.size(0)
         H = int(num_heads)
         dh = D // H
@@ -514,10 +346,9 @@ class AMPConvFunction(torch.autograd.Function):
             plan = choose_plan(L, D, H, shared, xq.dtype, gemm, xq2.numel(), _verdict(xq2, xq, maxima, 'x'),
                                _verdict(xkv2, xkv, maxima, 'xkv'), csr.active_nodes if Nq == csr.num_nodes else None,
                                torch.cuda.is_current_stream_capturing, dtype)
-            imgs = None
-            if plan.native:      # every weight image this call and its backward need, in one launch
-                ws = [w_in, w_out] if shared else [w_in[:D], w_in[D:], w_out]
-                imgs = proj_images([(w, False) for w in ws] + [(w, True) for w in ws])
+            # (weights: in-projection [, its K | V part], out-projection; native: every image this call and its
+            # backward need, in one launch)
+            proj = Projections(plan.native, [w_in, w_out] if shared else [w_in[:D], w_in[D:], w_out])
             sc = Scalars.for_forward(plan, maxima.get('x'), maxima.get('xkv'))
             lists = plan.lists
             kv = None
@@ -525,38 +356,28 @@ class AMPConvFunction(torch.autograd.Function):
                 # Q | K | V leave the in-projection as two fp16 planes scaled by a bound known before the product runs
                 # (max |x| times the largest absolute row sum of W, plus max |b|)
                 proj_out_bound(w_in, False, b_in, sc.x, sc.qkv_bound)
-                qkv = proj_rows_planes(xq2, imgs[0], sc.qkv_bound, b_in, amax=sc.x, out_amax=sc.obar, amax_col0=2 * D,
-                                       dh=dh)
+                qkv = proj_rows_planes(xq2, proj.image(0), sc.qkv_bound, b_in, amax=sc.x, out_amax=sc.obar,
+                                       amax_col0=2 * D, dh=dh)
             elif shared:
                 # (node lists: Q rows matter for nodes with in-edges, K / V rows for nodes with out-edges; the rows of
                 # nodes with neither are never read by an edge pass and stay unwritten)
-                qkv = (proj_rows(xq2, imgs[0], b_in, L=L, nodes=lists and lists['any'], amax=sc.x, out_amax=sc.obar)
-                       if plan.native else torch.addmm(b_in, xq2, w_in.t()))              # [N*L, 3D]
-            elif plan.native:
-                qkv = proj_rows(xq2, imgs[0], b_in[:D], amax=sc.x)
-                kv = proj_rows(xkv2, imgs[1], b_in[D:], amax=sc.xkv, out_amax=sc.obar)
+                qkv = proj.forward(0, xq2, b_in, nodes=lists and lists['any'], L=L, amax=sc.x,
+                                   out_amax=sc.obar)                                      # [N*L, 3D]
             else:
-                qkv = torch.addmm(b_in[:D], xq2, w_in[:D].t())         # [Nq*L, D]
-                kv = torch.addmm(b_in[D:], xkv2, w_in[D:].t())         # [Nk*L, 2D]
+                qkv = proj.forward(0, xq2, b_in[:D], amax=sc.x)                           # [Nq*L, D]
+                kv = proj.forward(1, xkv2, b_in[D:], amax=sc.xkv, out_amax=sc.obar)       # [Nk*L, 2D]
             Qv, Kv, Vv = _qkv_views(qkv, kv, L, D, dh)
             obar = torch.empty(Nq * L, D, dtype=xq.dtype, device=xq.device)
             if plan.edge == 'views':
                 sc.v_max.copy_(sc.qkv_bound)                 # (Scalars.for_forward)
             edge_fwd(plan, csr, Qv, Kv, Vv, Nq, obar, sc)
-            if lists:       # the rows of the nodes with in-edges; the others are zeroed without being read
-                y = proj_rows(obar, imgs[1], b_out, L=L, nodes=lists['in'])
-                _zero_unlisted(y, lists['in'], Nq, L)
-            elif plan.native:    # bias and the in-degree mask (rows nobody sends to stay exactly 0) in the epilogue
-                y = proj_rows(obar, imgs[1 if shared else 2], b_out, csr.rowptr, L, amax=sc.obar)
-            else:
-                y = torch.addmm(b_out, obar, w_out.t())
-                io = _lib.AMPCONV_BF16 if y.dtype == torch.bfloat16 else _lib.AMPCONV_F32
-                rc = lib.ampconv_mask_rows(y.data_ptr(), csr.rowptr.data_ptr(), Nq, L * D, io, _stream())
-                _lib.check(rc, 'ampconv_mask_rows')
+            # bias and the in-degree mask: rows nobody sends to stay exactly 0 (node lists: the rows of the nodes with
+            # in-edges are computed, the others are zeroed without being read)
+            dst = lists and lists['in']
+            y = proj.forward(-1, obar, b_out, mask=(dst[2] if dst else csr.rowptr, Nq), nodes=dst, L=L, amax=sc.obar)
         ctx.set_materialize_grads(False)     # no zero-filled [N*L, 3D] gradient for the qkv side output
         ctx.save_for_backward(xq2, xkv2, w_in, w_out, qkv, kv, obar)
-        ctx.csr, ctx.dims, ctx.plan, ctx.scalars = csr, (Nq, Nk), plan, sc
-        ctx.images_t = imgs[len(imgs) // 2:] if imgs else None     # the transposed images, for the input gradients
+        ctx.csr, ctx.dims, ctx.plan, ctx.scalars, ctx.proj = csr, (Nq, Nk), plan, sc, proj
         ctx.mark_non_differentiable(qkv)
         if kv is not None:
             ctx.mark_non_differentiable(kv)
@@ -567,11 +388,10 @@ class AMPConvFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, _dqkv=None, _dkv=None):
-        lib = _lib.load()
         if dy is None:
             return (None,) * 11
         xq2, xkv2, w_in, w_out, qkv, kv, obar = ctx.saved_tensors
-        csr, (Nq, Nk), plan, sc = ctx.csr, ctx.dims, ctx.plan, ctx.scalars
+        csr, (Nq, Nk), plan, sc, proj = ctx.csr, ctx.dims, ctx.plan, ctx.scalars, ctx.proj
         L, D, dh, shared = plan.L, plan.D, plan.dh, plan.shared
         dev = dy.device
         need_xq, need_xkv = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
@@ -583,36 +403,24 @@ class AMPConvFunction(torch.autograd.Function):
                 sc = sc.for_backward(st[0:1]) if plan.scaled else Scalars()
             if plan.qkv_to_f32:                 # the saved projections as fp32 for the exact edge passes
                 qkv = planes_to_f32(qkv, ctx.scalars.qkv_bound, dh)
-            # out-projection: rows with no in-edge contribute nothing (their obar is 0, and
-            # the bias gradient masks them explicitly)
-            if plan.native:
-                dw_out = torch.empty_like(w_out)
-                db_out = torch.empty(D, dtype=dy2.dtype, device=dev)
-                if plan.lists:   # the listed nodes ARE the ones that pass the mask; dObar is read for destinations only
-                    proj_wgrad(dy2, obar, dw_out, db_out, L=L, nodes=plan.lists['in'])
-                    dobar = proj_rows(dy2, ctx.images_t[-1], L=L, nodes=plan.lists['in'])
-                else:
-                    proj_wgrad(dy2, obar, dw_out, db_out, csr.rowptr, L, amax=(sc.dy, sc.obar))
-                    if plan.edge == 'planes':   # dObar / in-degree as two fp16 planes (the edge passes then carry no
-                        proj_out_bound(w_out, True, None, sc.dy, sc.dobar_bound)        # per-edge weight)
-                        sc.dobar_max.zero_()
-                        dobar = proj_rows_planes(dy2, ctx.images_t[-1], sc.dobar_bound, rowptr=csr.rowptr, L=L,
-                                                 row_scale=1, amax=sc.dy, out_amax=sc.dobar_max, dh=dh)
-                    elif plan.edge == 'views':  # fp32 dObar, its maximum recorded by the product that writes it
-                        sc.dobar_bound.zero_()
-                        dobar = proj_rows(dy2, ctx.images_t[-1], amax=sc.dy, out_amax=sc.dobar_bound)
-                        sc.dobar_max.copy_(sc.dobar_bound)       # (Scalars.for_forward)
-                    else:
-                        dobar = proj_rows(dy2, ctx.images_t[-1], amax=sc.dy)
-            else:
-                scratch = torch.empty((1 + _lib.COLSUM_BLOCKS) * D, dtype=torch.float32, device=dev)
-                io = _lib.AMPCONV_BF16 if dy2.dtype == torch.bfloat16 else _lib.AMPCONV_F32
-                rc = lib.ampconv_masked_colsum(dy2.data_ptr(), csr.rowptr.data_ptr(), Nq, L, D,
-                                               scratch.data_ptr(), io, _stream())
-                _lib.check(rc, 'ampconv_masked_colsum')
-                db_out = scratch[:D].to(dy2.dtype)
-                dw_out = _tn_matmul(dy2, obar)
-                dobar = dy2.mm(w_out)                                      # [Nq*L, D]
+            dst, both = (plan.lists['in'], plan.lists['any']) if plan.lists else (None, None)
+            # out-projection: rows with no in-edge contribute nothing (their obar is 0, and the bias gradient masks them
+            # explicitly; node lists: the listed nodes ARE the ones that pass the mask)
+            dw_out = torch.empty_like(w_out)
+            db_out = torch.empty(D, dtype=dy2.dtype, device=dev)
+            proj.weight_grad([(dy2, obar, (sc.dy, sc.obar))], dw_out, db_out, mask=None if dst else (csr.rowptr, Nq),
+                             nodes=dst, L=L)
+            if plan.edge == 'planes':   # dObar / in-degree as two fp16 planes (the edge passes then carry no per-edge
+                proj_out_bound(w_out, True, None, sc.dy, sc.dobar_bound)                                  # weight)
+                sc.dobar_max.zero_()
+                dobar = proj_rows_planes(dy2, proj.image(-1, True), sc.dobar_bound, rowptr=csr.rowptr, L=L, row_scale=1,
+                                         amax=sc.dy, out_amax=sc.dobar_max, dh=dh)
+            elif plan.edge == 'views':  # fp32 dObar, its maximum recorded by the product that writes it
+                sc.dobar_bound.zero_()
+                dobar = proj.input_grad(-1, dy2, amax=sc.dy, out_amax=sc.dobar_bound)
+                sc.dobar_max.copy_(sc.dobar_bound)       # (Scalars.for_forward)
+            else:                       # (node lists: dObar is read for destinations only; the other rows stay unwritten)
+                dobar = proj.input_grad(-1, dy2, nodes=dst, L=L, amax=sc.dy)         # [Nq*L, D]
             dOv = _view(dobar, 0, L, dh)
             dqkv = torch.empty(Nq * L, (3 if shared else 1) * D, dtype=dy2.dtype, device=dev)
             dkv = None if shared else torch.empty(Nk * L, 2 * D, dtype=dy2.dtype, device=dev)
@@ -627,49 +435,29 @@ class AMPConvFunction(torch.autograd.Function):
                     absmax(dqkv[:, D:], sc.dqkv)                # merged into the maximum of dQ
                 else:
                     sc.dkv = absmax(dkv)
-            # in_proj_bias gradient without a pass over all of dQKV: softmax rows sum to 1, so the
-            # column sum of dV over every source token equals the column sum of dObar over the rows
-            # that receive messages, and dObar = dY Wo is linear in dY, so that sum is (masked column sum of
-            # dY) Wo = db_out Wo: a [D] x [D, D] product instead of a second 20 GB reduction pass.  The K bias
-            # shifts every score of a row equally, i.e. has gradient exactly 0 (torch's autograd returns ~1e-9 noise)
-            db_v = None
-            if shared and dy2.dtype == torch.float32 and not plan.native:
-                db_v = scratch[:D] @ w_out
             del dobar, stats
-            if plan.native:
-                # weight and bias gradients in one pass each (the column sums ride on the rows the product reads
-                # anyway: all three thirds of in_proj_bias.grad are the true sums, as autograd's are)
-                dw_in = torch.empty_like(w_in)
-                db_in = torch.empty(3 * D, dtype=dy2.dtype, device=dev)
-                if plan.lists:   # the dQKV rows of a node without any edge are zeros (both edge passes wrote them)
-                    proj_wgrad(dqkv, xq2, dw_in, db_in, L=L, nodes=plan.lists['any'])
-                    dxq = dxkv = None
-                    if need_xq:
-                        dxq2 = proj_rows(dqkv, ctx.images_t[0], L=L, nodes=plan.lists['any'])
-                        _zero_unlisted(dxq2, plan.lists['any'], Nq, L)
-                        dxq = dxq2.view(Nq, L * D)
-                elif shared:
-                    proj_wgrad(dqkv, xq2, dw_in, db_in, amax=(sc.dqkv, sc.x))
-                    dxq = proj_rows(dqkv, ctx.images_t[0], amax=sc.dqkv).view(Nq, L * D) if need_xq else None
-                    dxkv = None
-                else:
-                    proj_wgrad(dqkv, xq2, dw_in[:D], db_in[:D], amax=(sc.dqkv, sc.x))
-                    proj_wgrad(dkv, xkv2, dw_in[D:], db_in[D:], amax=(sc.dkv, sc.xkv))
-                    dxq = proj_rows(dqkv, ctx.images_t[0], amax=sc.dqkv).view(Nq, L * D) if need_xq else None
-                    dxkv = proj_rows(dkv, ctx.images_t[1], amax=sc.dkv).view(Nk, L * D) if need_xkv else None
-            elif shared:
-                dw_in = _tn_matmul(dqkv, xq2)
-                if db_v is not None:
-                    db_in = torch.cat([dqkv[:, :D].sum(dim=0), torch.zeros_like(db_v), db_v])
-                else:
-                    db_in = dqkv.sum(dim=0)
-                dxq = dqkv.mm(w_in).view(Nq, L * D) if need_xq else None
-                dxkv = None
-            else:
-                dw_in = torch.cat([_tn_matmul(dqkv, xq2), _tn_matmul(dkv, xkv2)], dim=0)
-                db_in = torch.cat([dqkv.sum(dim=0), dkv.sum(dim=0)])
-                dxq = dqkv.mm(w_in[:D]).view(Nq, L * D) if need_xq else None
-                dxkv = dkv.mm(w_in[D:]).view(Nk, L * D) if need_xkv else None
+            # in-projection: weight and bias gradients in one pass each on the native side (the column sums ride on the
+            # rows the product reads anyway: all three thirds of in_proj_bias.grad are the true sums, as autograd's
+            # are; node lists: the dQKV rows of a node without any edge are zeros, both edge passes wrote them)
+            dw_in = torch.empty_like(w_in)
+            db_in = torch.empty(3 * D, dtype=dy2.dtype, device=dev)
+            terms = [(dqkv, xq2, (sc.dqkv, sc.x))] + ([] if shared else [(dkv, xkv2, (sc.dkv, sc.xkv))])
+            # fp32 library GEMMs, self-attention: in_proj_bias gradient without a pass over all of dQKV.  Softmax rows
+            # sum to 1, so the column sum of dV over every source token equals the column sum of dObar over the rows
+            # that receive messages, and dObar = dY Wo is linear in dY, so that sum is (masked column sum of dY) Wo =
+            # db_out Wo: a [D] x [D, D] product instead of a second 20 GB reduction pass.  The K bias shifts every score
+            # of a row equally, i.e. has gradient exactly 0 (torch's autograd returns ~1e-9 noise)
+            shortcut = shared and dy2.dtype == torch.float32 and not plan.native
+            db_v = db_out @ w_out if shortcut else None
+            proj.weight_grad(terms, dw_in, None if shortcut else db_in, nodes=both, L=L)
+            if shortcut:
+                torch.cat([dqkv[:, :D].sum(dim=0), torch.zeros_like(db_v), db_v], out=db_in)
+            dxq = dxkv = None
+            if need_xq:
+                dxq = proj.input_grad(0, dqkv, mask=both and (both[2], Nq), nodes=both, L=L,
+                                      amax=sc.dqkv).view(Nq, L * D)
+            if need_xkv and not shared:
+                dxkv = proj.input_grad(1, dkv, amax=sc.dkv).view(Nk, L * D)
         return dxq, dxkv, dw_in, db_in, dw_out, db_out, None, None, None, None, None
 
 

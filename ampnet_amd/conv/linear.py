@@ -11,7 +11,8 @@ Without the softmax the product re-associates: mean_e O_e = Q_d (mean_e K_s^T V_
 L x L scores never exist here.  Per SOURCE node and head one dh x dh matrix M_s = K_s^T V_s
 (`ampconv_linear_outer`), then the whole edge phase is a segment mean of M rows over the dst-sorted CSR
 (`ampconv_gather_segment_sum`, HBM-bound: D*dh floats per edge instead of 2*L*D), then Q_d Mbar_d per
-destination (`ampconv_linear_apply`); all three are HIP kernels of libampconv.so.  Backward is the transpose: dMbar_d = Q_d^T dObar_d,
+destination (`ampconv_linear_apply`); all three are HIP kernels of libampconv.so; the projections around them are the
+library-GEMM side of projection.Projections.  Backward is the transpose: dMbar_d = Q_d^T dObar_d,
 dM_s = sum over the out-edges of s of dMbar_d / deg_d (same kernel over the CSC with the per-edge
 1/deg weights), dK_s = V_s dM_s^T, dV_s = K_s dM_s, dQ_d = dObar_d Mbar_d^T.
 """
@@ -21,7 +22,8 @@ import torch
 
 from .. import _lib
 from ..graph import _stream
-from .functional import _tn_matmul, _view, gemm_precision
+from .functional import _qkv_views, _view
+from .projection import Projections, gemm_precision, masked_colsum
 
 
 def gather_segment_sum(rows, ptr, idx, n_out, weights=None, mean=False):
@@ -59,7 +61,6 @@ class LinearAMPConvFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xq, xkv, w_in, b_in, w_out, b_out, csr, num_heads, shared, gemm='fp32'):
-        lib = _lib.load()
         D = w_out.size(0)
         H = int(num_heads)
         dh = D // H
@@ -70,27 +71,26 @@ class LinearAMPConvFunction(torch.autograd.Function):
         dev = xq.device
         rs = 1.0 / math.sqrt(dh)
         xq2 = xq.contiguous().view(Nq * L, D)
+        # (the softmax-free path has always run its projections as library GEMMs: native=False)
+        proj = Projections(False, [w_in, w_out] if shared else [w_in[:D], w_in[D:], w_out])
         with torch.cuda.device(dev), gemm_precision(gemm):
             if shared:
-                qkv = torch.addmm(b_in, xq2, w_in.t())
                 xkv2, kv = xq2, None
-                Qv, Kv, Vv = (_view(qkv, i * D, L, dh) for i in range(3))
+                qkv = proj.forward(0, xq2, b_in)
             else:
                 xkv2 = xkv.contiguous().view(Nk * L, D)
-                qkv = torch.addmm(b_in[:D], xq2, w_in[:D].t())
-                kv = torch.addmm(b_in[D:], xkv2, w_in[D:].t())
-                Qv, Kv, Vv = _view(qkv, 0, L, dh), _view(kv, 0, L, dh), _view(kv, D, L, dh)
+                qkv = proj.forward(0, xq2, b_in[:D])
+                kv = proj.forward(1, xkv2, b_in[D:])
+            Qv, Kv, Vv = _qkv_views(qkv, kv, L, D, dh)
             M = _outer(Kv, Vv, Nk, L, D, H, 1.0, dev)                                  # K_s^T V_s
             Mbar = gather_segment_sum(M, csr.rowptr, csr.col, Nq, mean=True)           # the edge phase
             del M
             obar = torch.empty(Nq * L, D, dtype=torch.float32, device=dev)
             _apply(Qv, Mbar, False, Nq, L, D, H, rs, _view(obar, 0, L, dh))            # Q_d Mbar_d / sqrt(dh)
-            y = torch.addmm(b_out, obar, w_out.t())
-            rc = lib.ampconv_mask_rows(y.data_ptr(), csr.rowptr.data_ptr(), Nq, L * D, _lib.AMPCONV_F32, _stream())
-            _lib.check(rc, 'ampconv_mask_rows')
+            y = proj.forward(-1, obar, b_out, mask=(csr.rowptr, Nq), L=L)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(xq2, xkv2, w_in, w_out, qkv, kv, Mbar)       # obar is recomputed (one cheap pass)
-        ctx.csr, ctx.dims, ctx.shared, ctx.gemm = csr, (Nq, Nk, L, D, H), shared, gemm
+        ctx.csr, ctx.dims, ctx.shared, ctx.gemm, ctx.proj = csr, (Nq, Nk, L, D, H), shared, gemm, proj
         ctx.mark_non_differentiable(qkv)
         if kv is not None:
             ctx.mark_non_differentiable(kv)
@@ -98,11 +98,10 @@ class LinearAMPConvFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, _dqkv=None, _dkv=None):
-        lib = _lib.load()
         if dy is None:
             return (None,) * 10
         xq2, xkv2, w_in, w_out, qkv, kv, Mbar = ctx.saved_tensors
-        csr, shared = ctx.csr, ctx.shared
+        csr, shared, proj = ctx.csr, ctx.shared, ctx.proj
         Nq, Nk, L, D, H = ctx.dims
         dh = D // H
         dev = dy.device
@@ -110,51 +109,34 @@ class LinearAMPConvFunction(torch.autograd.Function):
         need_xq, need_xkv = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         with torch.cuda.device(dev), gemm_precision(ctx.gemm):
             dy2 = dy.contiguous().view(Nq * L, D)
-            scratch = torch.empty((1 + _lib.COLSUM_BLOCKS) * D, dtype=torch.float32, device=dev)
-            rc = lib.ampconv_masked_colsum(dy2.data_ptr(), csr.rowptr.data_ptr(), Nq, L, D, scratch.data_ptr(),
-                                           _lib.AMPCONV_F32, _stream())
-            _lib.check(rc, 'ampconv_masked_colsum')
-            db_out = scratch[:D].clone()
-            if shared:
-                Qv, Kv, Vv = (_view(qkv, i * D, L, dh) for i in range(3))
-            else:
-                Qv, Kv, Vv = _view(qkv, 0, L, dh), _view(kv, 0, L, dh), _view(kv, D, L, dh)
+            db_out = torch.empty(D, dtype=torch.float32, device=dev)
+            masked_colsum(dy2, csr.rowptr, Nq, L, db_out)
+            Qv, Kv, Vv = _qkv_views(qkv, kv, L, D, dh)
             obar = torch.empty(Nq * L, D, dtype=torch.float32, device=dev)
             _apply(Qv, Mbar, False, Nq, L, D, H, rs, _view(obar, 0, L, dh))
-            dw_out = _tn_matmul(dy2, obar)
+            dw_out = torch.empty_like(w_out)
+            proj.weight_grad([(dy2, obar, None)], dw_out, None)          # (db_out: above, before obar exists again)
             del obar
             # rows with no in-edge: obar = 0 and Mbar = 0, but dobar must not leak into dQ / dMbar
-            dobar = dy2.mm(w_out)
-            rc = lib.ampconv_mask_rows(dobar.data_ptr(), csr.rowptr.data_ptr(), Nq, L * D, _lib.AMPCONV_F32, _stream())
-            _lib.check(rc, 'ampconv_mask_rows')
+            dobar = proj.input_grad(-1, dy2, mask=(csr.rowptr, Nq), L=L)
             dOv = _view(dobar, 0, L, dh)
             dMbar = _outer(Qv, dOv, Nq, L, D, H, rs, dev)                               # Q^T dObar / sqrt(dh)
             # transpose of the segment mean: every out-edge of s brings dMbar[dst] / deg(dst)
             dM = gather_segment_sum(dMbar, csr.cscptr, csr.crow, Nk, weights=csr.cinv)
             del dMbar
             # gradients land in the packed buffers the projection GEMMs read
-            if shared:
-                dqkv = torch.empty(Nq * L, 3 * D, dtype=torch.float32, device=dev)
-                dQv, dKv, dVv = (_view(dqkv, i * D, L, dh) for i in range(3))
-            else:
-                dq2 = torch.empty(Nq * L, D, dtype=torch.float32, device=dev)
-                dkv = torch.empty(Nk * L, 2 * D, dtype=torch.float32, device=dev)
-                dQv, dKv, dVv = _view(dq2, 0, L, dh), _view(dkv, 0, L, dh), _view(dkv, D, L, dh)
+            dqkv = torch.empty(Nq * L, (3 if shared else 1) * D, dtype=torch.float32, device=dev)
+            dkv = None if shared else torch.empty(Nk * L, 2 * D, dtype=torch.float32, device=dev)
+            dQv, dKv, dVv = _qkv_views(dqkv, dkv, L, D, dh)
             _apply(dOv, Mbar, True, Nq, L, D, H, rs, dQv)                               # dQ = dObar Mbar^T / sqrt(dh)
             del dobar
             _apply(Vv, dM, True, Nk, L, D, H, 1.0, dKv)                                 # dK = V dM^T
             _apply(Kv, dM, False, Nk, L, D, H, 1.0, dVv)                                # dV = K dM
             del dM
-            if shared:
-                dw_in = _tn_matmul(dqkv, xq2)
-                db_in = dqkv.sum(dim=0)
-                dxq = dqkv.mm(w_in).view(Nq, L * D) if need_xq else None
-                dxkv = None
-            else:
-                dw_in = torch.cat([_tn_matmul(dq2, xq2), _tn_matmul(dkv, xkv2)], dim=0)
-                db_in = torch.cat([dq2.sum(dim=0), dkv.sum(dim=0)])
-                dxq = dq2.mm(w_in[:D]).view(Nq, L * D) if need_xq else None
-                dxkv = dkv.mm(w_in[D:]).view(Nk, L * D) if need_xkv else None
+            dw_in, db_in = torch.empty_like(w_in), torch.empty(3 * D, dtype=torch.float32, device=dev)
+            proj.weight_grad([(dqkv, xq2, None)] + ([] if shared else [(dkv, xkv2, None)]), dw_in, db_in)
+            dxq = proj.input_grad(0, dqkv).view(Nq, L * D) if need_xq else None
+            dxkv = proj.input_grad(1, dkv).view(Nk, L * D) if need_xkv and not shared else None
         return dxq, dxkv, dw_in, db_in, dw_out, db_out, None, None, None, None
 
 

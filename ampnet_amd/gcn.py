@@ -12,6 +12,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._lib import ptr as _ptr
 from .graph import EdgeCSR, _stream, graph_cache
 
 LONG_SEGMENT = _lib.GCN_LONG_SEGMENT      # a CSR / CSC segment from this length on is summed by whole workgroups
@@ -196,10 +197,6 @@ class _InputLinear(torch.autograd.Function):
                                                  _ptr(table), De, C, g.data_ptr(), _ld(g), dW.data_ptr(), _ptr(dtable),
                                                  ws.data_ptr(), nws, _stream()), 'ampconv_gcn_input_bwd')
         return None, dW, dtable, None, None
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def zscore_stats(x):

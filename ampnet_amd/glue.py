@@ -22,7 +22,6 @@ from .graph import _stream
 
 ACTIVATIONS = {'identity': 0, 'relu': 1, 'elu': 2}          # AMPCONV_ACT_* of include/ampconv.h
 POOLINGS = {'mean': 0, 'token0': 1}                         # AMPCONV_POOL_*
-_DTYPES = {torch.float32: _lib.AMPCONV_F32, torch.bfloat16: _lib.AMPCONV_BF16}
 _MASK64 = 2 ** 64 - 1
 
 
@@ -42,7 +41,7 @@ def mask_params(p, training=True):
 def _check(x, what):
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise ValueError(f'{what} needs a tensor on the GPU (ampnet_amd has no CPU fallback)')
-    if x.dtype not in _DTYPES:
+    if x.dtype not in _lib.DTYPES:
         raise ValueError(f'{what} takes float32 or bfloat16, got {x.dtype}')
 
 
@@ -65,7 +64,7 @@ class _ActDropout(torch.autograd.Function):
         y = torch.empty_like(x)
         with torch.cuda.device(x.device):
             _lib.check(lib.ampconv_act_dropout_fwd(x.data_ptr(), x.numel(), act, seed, thr, scale, y.data_ptr(),
-                                                   _DTYPES[x.dtype], _stream()), 'ampconv_act_dropout_fwd')
+                                                   _lib.DTYPES[x.dtype], _stream()), 'ampconv_act_dropout_fwd')
         if act != ACTIVATIONS['identity']:
             ctx.save_for_backward(y)                          # the OUTPUT: what the next layer saves as its input anyway
         ctx.args = (act, thr, scale, seed)
@@ -81,7 +80,7 @@ class _ActDropout(torch.autograd.Function):
         dx = torch.empty_like(dy)
         with torch.cuda.device(dy.device):
             _lib.check(lib.ampconv_act_dropout_bwd(dy.data_ptr(), None if y is None else y.data_ptr(), dy.numel(), act,
-                                                   seed, thr, scale, dx.data_ptr(), _DTYPES[dy.dtype], _stream()),
+                                                   seed, thr, scale, dx.data_ptr(), _lib.DTYPES[dy.dtype], _stream()),
                        'ampconv_act_dropout_bwd')
         return dx, None, None, None, None
 
@@ -95,7 +94,7 @@ class _ActDropoutPool(torch.autograd.Function):
         pooled = torch.empty(N, D, dtype=x.dtype, device=x.device)
         with torch.cuda.device(x.device):
             _lib.check(lib.ampconv_pool_fwd(x.data_ptr(), N, L, D, act, pooling, seed, thr, scale, pooled.data_ptr(),
-                                            _DTYPES[x.dtype], _stream()), 'ampconv_pool_fwd')
+                                            _lib.DTYPES[x.dtype], _stream()), 'ampconv_pool_fwd')
         if act != ACTIVATIONS['identity']:
             ctx.save_for_backward(x)                          # the layer output (the model's conv2_embedding)
         ctx.args = (N, L, D, act, pooling, thr, scale, seed, x.shape)
@@ -111,7 +110,7 @@ class _ActDropoutPool(torch.autograd.Function):
         dx = torch.empty(shape, dtype=dpooled.dtype, device=dpooled.device)
         with torch.cuda.device(dpooled.device):
             _lib.check(lib.ampconv_pool_bwd(None if x is None else x.data_ptr(), dpooled.data_ptr(), N, L, D, act, pooling,
-                                            seed, thr, scale, dx.data_ptr(), _DTYPES[dpooled.dtype], _stream()),
+                                            seed, thr, scale, dx.data_ptr(), _lib.DTYPES[dpooled.dtype], _stream()),
                        'ampconv_pool_bwd')
         return dx, None, None, None, None, None, None, None
 

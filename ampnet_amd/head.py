@@ -15,11 +15,11 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._lib import ptr as _ptr
 from .graph import _stream
 
 OUTPUTS = {'log_softmax': 0, 'sigmoid': 1}                  # AMPCONV_HEAD_* of include/ampconv.h
 MAX_CLASSES, MAX_MASKS, METRICS_SLOTS, LOSS_SHIFT = 64, 4, 13, 32
-_DTYPES = {torch.float32: _lib.AMPCONV_F32, torch.bfloat16: _lib.AMPCONV_BF16}
 _SUPPORTED = ('supported: pooled [N, D] float32 or bfloat16 on the GPU, weight [C, D] and bias [C] float32 on the same '
               f'device, 1 <= C <= {MAX_CLASSES} (ampnet_amd has no CPU fallback)')
 
@@ -28,7 +28,7 @@ def _check_head(pooled, weight, bias, what):
     for name, t in (('pooled', pooled), ('weight', weight), ('bias', bias)):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
             raise ValueError(f'{what}: {name} has to be a tensor on the GPU; {_SUPPORTED}')
-    if pooled.dtype not in _DTYPES:
+    if pooled.dtype not in _lib.DTYPES:
         raise ValueError(f'{what}: pooled is {pooled.dtype}; {_SUPPORTED}')
     if weight.dtype != torch.float32 or bias.dtype != torch.float32:
         raise ValueError(f'{what}: weight is {weight.dtype}, bias is {bias.dtype}; {_SUPPORTED}')
@@ -57,10 +57,6 @@ def _workspace(lib, N, D, C, device):
     return torch.empty(max(int(lib.ampconv_head_workspace_bytes(N, D, C)), 16), dtype=torch.uint8, device=device)
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 class _Head(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pooled, weight, bias, kind):
@@ -72,7 +68,7 @@ class _Head(torch.autograd.Function):
         out = torch.empty(N, C, dtype=torch.float32, device=pooled.device)
         with torch.cuda.device(pooled.device):
             _lib.check(lib.ampconv_head_fwd(pooled.data_ptr(), N, D, stride, weight.data_ptr(), bias.data_ptr(), C, kind,
-                                            out.data_ptr(), _DTYPES[pooled.dtype], _stream()), 'ampconv_head_fwd')
+                                            out.data_ptr(), _lib.DTYPES[pooled.dtype], _stream()), 'ampconv_head_fwd')
         ctx.save_for_backward(pooled, weight, out)
         ctx.args = (kind, stride)
         return out
@@ -92,7 +88,7 @@ class _Head(torch.autograd.Function):
         with torch.cuda.device(pooled.device):
             _lib.check(lib.ampconv_head_bwd(pooled.data_ptr(), N, D, stride, weight.data_ptr(), C, kind, dout.data_ptr(),
                                             out.data_ptr(), _ptr(dpooled), dW.data_ptr(), db.data_ptr(), ws.data_ptr(),
-                                            ws.numel(), _DTYPES[pooled.dtype], _stream()), 'ampconv_head_bwd')
+                                            ws.numel(), _lib.DTYPES[pooled.dtype], _stream()), 'ampconv_head_bwd')
         return dpooled, dW, db, None
 
 
@@ -147,7 +143,7 @@ class _SaintNLL(torch.autograd.Function):
         with torch.cuda.device(dev):
             _lib.check(lib.ampconv_head_nll_fwd(pooled.data_ptr(), N, D, stride, weight.data_ptr(), bias.data_ptr(), C,
                                                 y.data_ptr(), _ptr(w), _ptr(masks), M, grad_mask, _ptr(logp),
-                                                _ptr(metrics), scratch.data_ptr(), loss.data_ptr(), _DTYPES[pooled.dtype],
+                                                _ptr(metrics), scratch.data_ptr(), loss.data_ptr(), _lib.DTYPES[pooled.dtype],
                                                 _stream()), 'ampconv_head_nll_fwd')
         ctx.save_for_backward(pooled, weight, bias, y, w, masks)
         ctx.args = (stride, M, grad_mask)
@@ -172,7 +168,7 @@ class _SaintNLL(torch.autograd.Function):
             _lib.check(lib.ampconv_head_nll_bwd(pooled.data_ptr(), N, D, stride, weight.data_ptr(), bias.data_ptr(), C,
                                                 y.data_ptr(), _ptr(w), _ptr(masks), M, grad_mask, g.data_ptr(),
                                                 _ptr(dpooled), dW.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                _DTYPES[pooled.dtype], _stream()), 'ampconv_head_nll_bwd')
+                                                _lib.DTYPES[pooled.dtype], _stream()), 'ampconv_head_nll_bwd')
         return dpooled, dW, db, None, None, None, None, None, None, None
 
 

@@ -35,7 +35,6 @@ from ..stats import tensor_stats
 from ..graph import _stream
 
 
-_STORAGE = {torch.float32: _lib.AMPCONV_F32, torch.bfloat16: _lib.AMPCONV_BF16}
 
 
 class _BuildTokens(torch.autograd.Function):
@@ -55,7 +54,7 @@ class _BuildTokens(torch.autograd.Function):
         out = torch.empty(N, L, De + 1, dtype=dtype, device=x.device)
         with torch.cuda.device(x.device):
             _lib.check(lib.ampconv_feat_build_as(x.data_ptr(), mean.data_ptr(), inv_std.data_ptr(), idx.data_ptr(),
-                                                 table.data_ptr(), N, Fdim, L, De, out.data_ptr(), _STORAGE[dtype],
+                                                 table.data_ptr(), N, Fdim, L, De, out.data_ptr(), _lib.DTYPES[dtype],
                                                  _stream()), 'ampconv_feat_build_as')
         ctx.save_for_backward(idx)
         ctx.dims = (N, L, De, table.size(0))
@@ -71,7 +70,7 @@ class _BuildTokens(torch.autograd.Function):
         dout = dout.to(ctx.storage).contiguous()
         with torch.cuda.device(dout.device):
             _lib.check(lib.ampconv_feat_table_grad_from(dout.data_ptr(), idx.data_ptr(), N, L, De, Fdim, dtable.data_ptr(),
-                                                        _STORAGE[ctx.storage], _stream()), 'ampconv_feat_table_grad_from')
+                                                        _lib.DTYPES[ctx.storage], _stream()), 'ampconv_feat_table_grad_from')
         return dtable, None, None, None, None, None
 
 
@@ -80,7 +79,7 @@ class FeatureTokens(nn.Module):
 
     def __init__(self, num_node_features, feat_emb_dim, num_sampled_vectors, seed=0, token_dtype=torch.float32):
         super().__init__()
-        if token_dtype not in _STORAGE:
+        if token_dtype not in _lib.DTYPES:
             raise ValueError(f'tokens are written as float32 or bfloat16, not {token_dtype}')
         self.token_dtype = token_dtype
         self.feature_embedding_table = nn.Embedding(num_embeddings=num_node_features, embedding_dim=feat_emb_dim)
@@ -164,7 +163,7 @@ class AMPGCN(nn.Module):
                  dropout_adj_rate=0.1, feature_repeats=5, seed=0, fused_glue=False, fused_head=False, layer_norm=False,
                  storage_dtype=torch.float32):
         super().__init__()
-        if storage_dtype not in _STORAGE:
+        if storage_dtype not in _lib.DTYPES:
             raise ValueError(f'storage_dtype is torch.float32 or torch.bfloat16, got {storage_dtype}')
         self.storage_dtype = storage_dtype
         assert embedding_dim == feat_emb_dim + val_emb_dim, \

@@ -20,14 +20,11 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .glue import ACTIVATIONS, POOLINGS, _DTYPES, _MASK64, _SeededSite, _check, _code, _fresh_seed, mask_params
+from ._lib import ptr as _ptr
+from .glue import ACTIVATIONS, POOLINGS, _MASK64, _SeededSite, _check, _code, _fresh_seed, mask_params
 from .graph import _stream
 
 MAX_EMBED_DIM = 1024                                        # AMPCONV_NORM_MAX_D of include/ampconv.h
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def _workspace(lib, tokens, D, device):
@@ -50,7 +47,7 @@ class _NormActDropout(torch.autograd.Function):
         stats = torch.empty(T, 2, dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
             _lib.check(lib.ampconv_norm_fwd(x.data_ptr(), T, D, _ptr(weight), _ptr(bias), eps, act, seed, thr, scale,
-                                            y.data_ptr(), stats.data_ptr(), _DTYPES[x.dtype], _stream()),
+                                            y.data_ptr(), stats.data_ptr(), _lib.DTYPES[x.dtype], _stream()),
                        'ampconv_norm_fwd')
         ctx.save_for_backward(x, stats, weight, bias)         # x: the layer output (the model's convN_embedding)
         ctx.args = (T, D, act, thr, scale, seed)
@@ -69,7 +66,7 @@ class _NormActDropout(torch.autograd.Function):
         with torch.cuda.device(x.device):
             _lib.check(lib.ampconv_norm_bwd(x.data_ptr(), dy.data_ptr(), stats.data_ptr(), T, D, _ptr(weight), _ptr(bias),
                                             act, seed, thr, scale, dx.data_ptr(), _ptr(dw), _ptr(db), _ptr(ws),
-                                            0 if ws is None else ws.numel(), _DTYPES[x.dtype], _stream()),
+                                            0 if ws is None else ws.numel(), _lib.DTYPES[x.dtype], _stream()),
                        'ampconv_norm_bwd')
         return dx, dw, db, None, None, None, None, None, None
 
@@ -84,7 +81,7 @@ class _NormActDropoutPool(torch.autograd.Function):
         stats = torch.empty(N * (1 if pooling == POOLINGS['token0'] else L), 2, dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
             _lib.check(lib.ampconv_norm_pool_fwd(x.data_ptr(), N, L, D, _ptr(weight), _ptr(bias), eps, act, pooling, seed,
-                                                 thr, scale, pooled.data_ptr(), stats.data_ptr(), _DTYPES[x.dtype],
+                                                 thr, scale, pooled.data_ptr(), stats.data_ptr(), _lib.DTYPES[x.dtype],
                                                  _stream()), 'ampconv_norm_pool_fwd')
         ctx.save_for_backward(x, stats, weight, bias)
         ctx.args = (N, L, D, act, pooling, thr, scale, seed)
@@ -103,7 +100,7 @@ class _NormActDropoutPool(torch.autograd.Function):
         with torch.cuda.device(x.device):
             _lib.check(lib.ampconv_norm_pool_bwd(x.data_ptr(), dpooled.data_ptr(), stats.data_ptr(), N, L, D, _ptr(weight),
                                                  _ptr(bias), act, pooling, seed, thr, scale, dx.data_ptr(), _ptr(dw),
-                                                 _ptr(db), _ptr(ws), 0 if ws is None else ws.numel(), _DTYPES[x.dtype],
+                                                 _ptr(db), _ptr(ws), 0 if ws is None else ws.numel(), _lib.DTYPES[x.dtype],
                                                  _stream()), 'ampconv_norm_pool_bwd')
         return dx, dw, db, None, None, None, None, None, None, None, None
 
@@ -113,7 +110,7 @@ def _site_args(x, embed_dim, weight, bias, eps, p, activation, training, seed, w
     first, the device last."""
     if not isinstance(x, torch.Tensor):
         raise ValueError(f'{what} needs a tensor, got {type(x).__name__}')
-    if x.dtype not in _DTYPES:
+    if x.dtype not in _lib.DTYPES:
         raise ValueError(f'{what} takes float32 or bfloat16, got {x.dtype}')
     act = _code(ACTIVATIONS, activation, 'activation')
     D = int(embed_dim)

@@ -34,7 +34,6 @@ MAX_TENSORS = _lib.ADAM_MAX_TENSORS      # descriptors per launch (AMPCONV_ADAM_
 
 _SUPPORTED = ('FusedAdam supports contiguous float32 or bfloat16 parameters on the GPU with dense float32 or bfloat16 gradients '
               'of the same shape and device, without amsgrad, maximize or capturable (ampnet_amd has no CPU or eager fallback)')
-_DTYPES = {torch.float32: _lib.AMPCONV_F32, torch.bfloat16: _lib.AMPCONV_BF16}
 _FP32_STATE = ('exp_avg', 'exp_avg_sq', 'master')
 _REFUSED = ('amsgrad', 'maximize', 'capturable')
 _ENTRY = ctypes.sizeof(_lib.AdamTensor)
@@ -156,7 +155,7 @@ class FusedAdam(torch.optim.Optimizer):
 
     @staticmethod
     def _check_pair(p, g):
-        if p.dtype not in _DTYPES:
+        if p.dtype not in _lib.DTYPES:
             raise ValueError(f'a parameter is {p.dtype}; {_SUPPORTED}')
         if not p.is_cuda:
             raise ValueError(f'a parameter is on {p.device}, not on the GPU; {_SUPPORTED}')
@@ -164,7 +163,7 @@ class FusedAdam(torch.optim.Optimizer):
             raise ValueError(f'a parameter of shape {tuple(p.shape)} is not contiguous; {_SUPPORTED}')
         if not isinstance(g, torch.Tensor) or g.is_sparse or g.layout != torch.strided:
             raise ValueError(f'a gradient is {"sparse" if isinstance(g, torch.Tensor) else type(g).__name__}; {_SUPPORTED}')
-        if g.dtype not in _DTYPES or g.device != p.device or g.shape != p.shape:
+        if g.dtype not in _lib.DTYPES or g.device != p.device or g.shape != p.shape:
             raise ValueError(f'a gradient is {g.dtype} {tuple(g.shape)} on {g.device} for a {tuple(p.shape)} parameter on '
                              f'{p.device}; {_SUPPORTED}')
 
@@ -224,7 +223,7 @@ class FusedAdam(torch.optim.Optimizer):
                 tail = (p.numel(), lr / (1.0 - beta1 ** t), 1.0 / math.sqrt(1.0 - beta2 ** t))
                 if mixed:
                     master = st['master'].data_ptr() if p.dtype == torch.bfloat16 and p.numel() else None
-                    entries.append(row + (master,) + tail + (_DTYPES[p.dtype], _DTYPES[g.dtype]))
+                    entries.append(row + (master,) + tail + (_lib.DTYPES[p.dtype], _lib.DTYPES[g.dtype]))
                 else:
                     entries.append(row + tail)
         want_norm = self.max_grad_norm is not None or self.track_grad_norm

@@ -12,7 +12,7 @@ This module runs ONE graph un-sampled on W ranks:
     local;
   * backward: destination pass local; the source pass produces dK|dV partial sums for EVERY source
     node from the local edges, ONE reduce-scatter (sum) returns each rank the rows of its own nodes;
-    the projection GEMMs are local and the parameter gradients are SUMS over ranks
+    the projections (conv/projection.py, Q part and K|V part apart) are local and the parameter gradients are SUMS over ranks
     (`GradientAllReducer(..., average=False)`).
 
 Two collectives per layer and direction-pair, each moving 2*N*L*D elements: at BASELINE config 4
@@ -31,7 +31,8 @@ import torch.distributed as dist
 
 from . import _lib
 from .conv import functional as F_
-from .graph import EdgeCSR, _stream
+from .conv.projection import Projections
+from .graph import EdgeCSR
 
 
 class NodePartition:
@@ -118,7 +119,6 @@ class NodePartition:
 class _PartitionedFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_local, w_in, b_in, w_out, b_out, csr, num_heads, part, dtype, gemm='native'):
-        lib = _lib.load()
         D = w_out.size(0)
         H = int(num_heads)
         dh = D // H
@@ -126,84 +126,54 @@ class _PartitionedFunction(torch.autograd.Function):
         nl, NP = part.n_local, part.n_padded
         dev = x_local.device
         x2 = x_local.contiguous().view(nl * L, D)
-        native = F_.proj_native(gemm, x_local.dtype, D)                 # libampconv's own projection kernels
         with torch.cuda.device(dev):
+            # (weights: Q part and K | V part of the in-projection, out-projection)
+            proj = Projections(F_.proj_native(gemm, x_local.dtype, D), [w_in[:D], w_in[D:], w_out])
             # K|V of the local rows first, their all-gather in flight while the Q projection runs
-            kv_loc = (F_.proj_rows(x2, F_.proj_image(w_in[D:]), b_in[D:]) if native
-                      else torch.addmm(b_in[D:], x2, w_in[D:].t()))      # [nl*L, 2D]
+            kv_loc = proj.forward(1, x2, b_in[D:])                      # [nl*L, 2D]
             kv_all, work = part.all_gather_rows_start(kv_loc)           # every node's K|V, [NP*L, 2D]
-            qkv = (F_.proj_rows(x2, F_.proj_image(w_in[:D]), b_in[:D]) if native
-                   else torch.addmm(b_in[:D], x2, w_in[:D].t()))         # Q of the local rows, [nl*L, D]
+            qkv = proj.forward(0, x2, b_in[:D])                         # Q of the local rows, [nl*L, D]
             work.wait()
             del kv_loc
-            Qv = F_._view(qkv, 0, L, dh)
-            Kv, Vv = F_._view(kv_all, 0, L, dh), F_._view(kv_all, D, L, dh)
+            Qv, Kv, Vv = F_._qkv_views(qkv, kv_all, L, D, dh)
             obar = torch.empty(nl * L, D, dtype=x_local.dtype, device=dev)
             F_.edge_forward(Qv, Kv, Vv, csr, nl, L, D, H, obar, dtype=dtype)
-            if native:
-                y = F_.proj_rows(obar, F_.proj_image(w_out), b_out, csr.rowptr, L)
-            else:
-                y = torch.addmm(b_out, obar, w_out.t())
-                rc = lib.ampconv_mask_rows(y.data_ptr(), csr.rowptr.data_ptr(), nl, L * D, _lib.AMPCONV_F32, _stream())
-                _lib.check(rc, 'ampconv_mask_rows')
+            y = proj.forward(-1, obar, b_out, mask=(csr.rowptr, nl), L=L)
         ctx.save_for_backward(x2, w_in, w_out, qkv, kv_all, obar)
-        ctx.csr, ctx.dims, ctx.part, ctx.dtype, ctx.native = csr, (nl, NP, L, D, H), part, dtype, native
+        ctx.csr, ctx.dims, ctx.part, ctx.dtype, ctx.proj = csr, (nl, NP, L, D, H), part, dtype, proj
         return y.view(nl, L * D)
 
     @staticmethod
     def backward(ctx, dy):
-        lib = _lib.load()
         x2, w_in, w_out, qkv, kv_all, obar = ctx.saved_tensors
-        csr, part = ctx.csr, ctx.part
+        csr, part, proj = ctx.csr, ctx.part, ctx.proj
         nl, NP, L, D, H = ctx.dims
         dh = D // H
         dev = dy.device
         with torch.cuda.device(dev):
             dy2 = dy.contiguous().view(nl * L, D)
-            native = ctx.native
-            if native:
-                dw_out, db_out = torch.empty_like(w_out), torch.empty(D, dtype=torch.float32, device=dev)
-                F_.proj_wgrad(dy2, obar, dw_out, db_out, csr.rowptr, L)
-                dobar = F_.proj_rows(dy2, F_.proj_image(w_out, transpose=True))
-            else:
-                scratch = torch.empty((1 + _lib.COLSUM_BLOCKS) * D, dtype=torch.float32, device=dev)
-                rc = lib.ampconv_masked_colsum(dy2.data_ptr(), csr.rowptr.data_ptr(), nl, L, D, scratch.data_ptr(),
-                                               _lib.AMPCONV_F32, _stream())
-                _lib.check(rc, 'ampconv_masked_colsum')
-                db_out = scratch[:D].clone()
-                dw_out = F_._tn_matmul(dy2, obar)
-                dobar = dy2.mm(w_out)
-            Qv, dOv = F_._view(qkv, 0, L, dh), F_._view(dobar, 0, L, dh)
-            Kv, Vv = F_._view(kv_all, 0, L, dh), F_._view(kv_all, D, L, dh)
+            dw_out, db_out = torch.empty_like(w_out), torch.empty(D, dtype=torch.float32, device=dev)
+            proj.weight_grad([(dy2, obar, None)], dw_out, db_out, mask=(csr.rowptr, nl), L=L)
+            dobar = proj.input_grad(-1, dy2)
+            dOv = F_._view(dobar, 0, L, dh)
             dq = torch.empty(nl * L, D, dtype=torch.float32, device=dev)
             dkv_all = torch.empty(NP * L, 2 * D, dtype=torch.float32, device=dev)     # partial sums, all sources
-            dQv = F_._view(dq, 0, L, dh)
-            dKv, dVv = F_._view(dkv_all, 0, L, dh), F_._view(dkv_all, D, L, dh)
+            Qv, Kv, Vv = F_._qkv_views(qkv, kv_all, L, D, dh)
+            dQv, dKv, dVv = F_._qkv_views(dq, dkv_all, L, D, dh)
             plan = F_.LayerPlan(L, D, H, dtype=ctx.dtype)                   # the plain pair
             stats = F_.edge_bwd_dst(plan, csr, Qv, Kv, Vv, dOv, nl, dQv, F_.Scalars())
             F_.edge_bwd_src(plan, csr, Qv, Kv, Vv, dOv, NP, dKv, dVv, stats, F_.Scalars())
             del dobar, stats
             # this rank's rows of dK|dV, summed over ranks: in flight while the Q-side products run
             dkv, work = part.reduce_scatter_rows_start(dkv_all)
-            if native:
-                dw_in, db_in = torch.empty_like(w_in), torch.empty(3 * D, dtype=torch.float32, device=dev)
-                F_.proj_wgrad(dq, x2, dw_in[:D], db_in[:D])
-                dx = F_.proj_rows(dq, F_.proj_image(w_in[:D], transpose=True)) if ctx.needs_input_grad[0] else None
-                work.wait()
-                del dkv_all
-                F_.proj_wgrad(dkv, x2, dw_in[D:], db_in[D:])
-                if dx is not None:
-                    dx = dx.add_(F_.proj_rows(dkv, F_.proj_image(w_in[D:], transpose=True))).view(nl, L * D)
-            else:
-                dw_q = F_._tn_matmul(dq, x2)
-                db_q = dq.sum(dim=0)
-                dx = dq.mm(w_in[:D]) if ctx.needs_input_grad[0] else None
-                work.wait()
-                del dkv_all
-                dw_in = torch.cat([dw_q, F_._tn_matmul(dkv, x2)], dim=0)
-                db_in = torch.cat([db_q, dkv.sum(dim=0)])
-                if dx is not None:
-                    dx = dx.addmm_(dkv, w_in[D:]).view(nl, L * D)
+            dw_in, db_in = torch.empty_like(w_in), torch.empty(3 * D, dtype=torch.float32, device=dev)
+            proj.weight_grad([(dq, x2, None)], dw_in[:D], db_in[:D])
+            dx = proj.input_grad(0, dq) if ctx.needs_input_grad[0] else None
+            work.wait()
+            del dkv_all
+            proj.weight_grad([(dkv, x2, None)], dw_in[D:], db_in[D:])
+            if dx is not None:
+                dx = proj.input_grad(1, dkv, into=dx).view(nl, L * D)
         return dx, dw_in, db_in, dw_out, db_out, None, None, None, None, None
 
 

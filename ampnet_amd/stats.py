@@ -29,7 +29,6 @@ MAX_TENSORS = _lib.STATS_MAX_TENSORS     # descriptors per launch; more tensors 
 MAX_BINS = _lib.STATS_MAX_BINS
 MAX_RANKS = _lib.STATS_MAX_RANKS         # order statistics per call, the median included
 
-_DTYPES = {torch.float32: _lib.AMPCONV_F32, torch.bfloat16: _lib.AMPCONV_BF16}
 _SUPPORTED = ('tensor_stats supports contiguous float32 or bfloat16 tensors on one GPU, 0 <= bins <= '
               f'{MAX_BINS} and at most {MAX_RANKS} order statistics, the median included (ampnet_amd has no CPU or eager '
               'fallback)')
@@ -159,7 +158,7 @@ def tensor_stats(tensors, bins=0, range=None, median=False, quantiles=()):
             raise ValueError(f'got a {type(t).__name__}; {_SUPPORTED}')
         if not t.is_cuda:
             raise ValueError(f'a tensor is on {t.device}, not on the GPU; {_SUPPORTED}')
-        if t.dtype not in _DTYPES:
+        if t.dtype not in _lib.DTYPES:
             raise ValueError(f'a tensor is {t.dtype}; {_SUPPORTED}')
         if not t.is_contiguous():
             raise ValueError(f'a tensor of shape {tuple(t.shape)} is not contiguous; {_SUPPORTED}')
@@ -188,7 +187,7 @@ def tensor_stats(tensors, bins=0, range=None, median=False, quantiles=()):
             sections[name] = size
             size += _round8(nbytes)
     lib = _lib.load()
-    table = (_lib.StatsTensor * n)(*[(t.data_ptr() if t.numel() else None, t.numel(), _DTYPES[t.dtype]) for t in items])
+    table = (_lib.StatsTensor * n)(*[(t.data_ptr() if t.numel() else None, t.numel(), _lib.DTYPES[t.dtype]) for t in items])
     with torch.cuda.device(device):
         out = torch.zeros(size, dtype=torch.uint8, device=device)            # the counts start at zero
         base = out.data_ptr()

@@ -193,6 +193,65 @@ def test_proj_wgrad_into_row_block_views():
     assert _err(db, torch.cat([dq, dkv], 1).double().sum(0)) < 1e-6
 
 
+@pytest.mark.parametrize('D', [8, 12])
+def test_projection_layer_both_sides_match_fp64(D):
+    """conv/projection.py's Projections -- forward, input_grad, weight_grad, and the masks of each -- on libampconv's
+    kernels and as library GEMMs, against float64 products: 5 nodes x 3 rows, node 2 without an in-edge; the unshared
+    pair are the views W[:D] / W[D:] of one packed weight.  Bars: those of the fp32 tests above."""
+    from ampnet_amd.conv.projection import Projections
+    dev = _dev()
+    n, L, empty = 5, 3, 2
+    M = n * L
+    rp, has = _rowptr(n, (empty,), dev)
+    keep = has.to(dev).repeat_interleave(L)
+    g = torch.Generator(device=dev).manual_seed(D)
+
+    def rand(*shape, scale=1.0):
+        return torch.randn(*shape, device=dev, generator=g) * scale
+    W, Wo, b, bo = rand(3 * D, D, scale=0.1), rand(D, D, scale=0.1), rand(3 * D), rand(D)
+    xq, xkv, gq, gkv, dy = rand(M, D), rand(M, D), rand(M, D), rand(M, 2 * D), rand(M, D)
+    obar = rand(M, D) * keep[:, None]                     # (rows of a node without an in-edge are zeros, as Obar's are)
+    d, flag = torch.double, keep[:, None].double()
+    refs = {
+        'q': xq.to(d) @ W[:D].to(d).t() + b[:D].to(d), 'kv': xkv.to(d) @ W[D:].to(d).t() + b[D:].to(d),
+        'y': (obar.to(d) @ Wo.to(d).t() + bo.to(d)) * flag, 'dxkv': gkv.to(d) @ W[D:].to(d),
+        'dobar': (dy.to(d) @ Wo.to(d)) * flag, 'dx': gq.to(d) @ W[:D].to(d) + gkv.to(d) @ W[D:].to(d),
+        'dw_in': torch.cat([gq.to(d).t() @ xq.to(d), gkv.to(d).t() @ xkv.to(d)]),
+        'dw_out': (dy.to(d) * flag).t() @ obar.to(d),
+    }
+    lib = {      # torch's own fp32 products of the same operands: the yardstick of the bar
+        'q': torch.addmm(b[:D], xq, W[:D].t()), 'kv': torch.addmm(b[D:], xkv, W[D:].t()),
+        'y': torch.addmm(bo, obar, Wo.t()) * keep[:, None], 'dxkv': gkv @ W[D:], 'dobar': (dy @ Wo) * keep[:, None],
+        'dx': gq @ W[:D] + gkv @ W[D:], 'dw_in': torch.cat([gq.t() @ xq, gkv.t() @ xkv]), 'dw_out': dy.t() @ obar,
+    }
+    got = {}
+    for native in (True, False):
+        proj = Projections(native, [W[:D], W[D:], Wo])
+        dw_in, db_in = torch.empty(3 * D, D, device=dev), torch.empty(3 * D, device=dev)
+        dw_out, db_out = torch.empty(D, D, device=dev), torch.empty(D, device=dev)
+        proj.weight_grad([(gq, xq, None), (gkv, xkv, None)], dw_in, db_in)
+        proj.weight_grad([(dy, obar, None)], dw_out, db_out, mask=(rp, n), L=L)
+        out = got[native] = {
+            'q': proj.forward(0, xq, b[:D]), 'kv': proj.forward(1, xkv, b[D:]),
+            'y': proj.forward(-1, obar, bo, mask=(rp, n), L=L), 'dxkv': proj.input_grad(1, gkv),
+            'dobar': proj.input_grad(-1, dy, mask=(rp, n), L=L),
+            'dx': proj.input_grad(1, gkv, into=proj.input_grad(0, gq)), 'dw_in': dw_in, 'dw_out': dw_out,
+        }
+        for name, ref in refs.items():
+            lib_err = _err(lib[name], ref)
+            assert _err(out[name], ref) <= 2 * lib_err + 1e-7, (native, name, _err(out[name], ref), lib_err)
+        for cs, src in ((db_in[:D], gq), (db_in[D:], gkv), (db_out, dy * keep[:, None])):
+            assert float((cs.double() - src.double().sum(0)).abs().max()) <= 1e-6 * float(src.abs().sum(0).max()) + 1e-6
+        for name in ('y', 'dobar'):             # the mask: the rows of node `empty`, and only those, are exactly 0
+            assert torch.equal((out[name] == 0).all(1), ~keep), (native, name)
+    for name in ('y', 'dobar'):                 # ... the same rows, bit for bit, on both sides
+        assert torch.equal(got[True][name][~keep], got[False][name][~keep])
+    # the GEMM side leaves the column sums to a caller that has them from elsewhere
+    dw2 = torch.empty(D, D, device=dev)
+    Projections(False, [Wo]).weight_grad([(dy, obar, None)], dw2, None, mask=(rp, n), L=L)
+    assert torch.equal(dw2, got[False]['dw_out'])
+
+
 def test_unsupported_shapes_are_refused_not_miscomputed():
     from ampnet_amd import _lib
     lib = _lib.load()
