@@ -16,7 +16,8 @@
 // with ONE exponent e per tensor, e = 14 - floor(log2 bound) for a device-side bound of max |x| (plane_scale: the scaled
 // maximum lies below 2^15).  Views keep the strides of the fp32 tensor the planes replace (in 4-byte elements).
 //
-// Structure = edge_mfma_bf16.hip with two plane images per tile: one wavefront owns one (row, head) unit, streams a
+// Structure = the one-wave-per-unit skeleton of edge_wave16.h with two plane images per tile: one wavefront owns one
+// (row, head) unit, streams a
 // pair of 20 x 128-byte tiles per edge (five full wave-wide 16-B/lane loads) through registers into private LDS
 // images (per plane the swizzled 64-byte-row image of the bf16 kernels, plane16.h: conflict-free ds_write_b128,
 // ds_read_b128 and transposed reads), channel-product fragments are one ds_read_b128 per plane, token-product fragments two
@@ -26,19 +27,17 @@
 // kernels: 20 log2-sum-exp + 20 delta floats per edge and head, filed at the edge's CSC position by the destination pass):
 // with them the source pass's softmax is element-wise -- its three 16-lane reductions per row are a third of its
 // vector instructions, and these passes are bound by vector issue and by the clock the chip holds under them.
-#include "plane16.h"
+// This file: the format policy (FmtP), the forward and destination kernels as wrappers of the shared bodies, and the
+// source pass, which is this format's own algorithm.
+#include "edge_wave16.h"
 
 namespace {
-using namespace plane16;      // plane_scale, split2, frag_sumsq, the swizzled plane image (plane_off, rowfrag, colfrag), TR_*
+using namespace wave16;       // the skeleton; plane16: plane_scale, split2, frag_sumsq, the swizzled plane image (plane_off, rowfrag, colfrag), TR_*
 
-constexpr int kWavesPerBlock = 4;
-constexpr int DH = 32;
 // HALF (dh = 16, BASELINE config 3's head width): the head's slot is 64 bytes (16 hi, 16 lo); its 16 channels occupy the
 // lower half of every 32-channel plane row, the upper half is never written (the images are zeroed once per unit: the
 // 32-deep channel contraction is zero-padded) and only channel tile mc = 0 exists.  Half the bytes per (edge, head) at the
 // same vector work: these shapes are bound by instruction issue, not by HBM.
-constexpr int kRowBytes = DH * 2;                      // one plane of a token row
-constexpr int kPlaneBytes = kLmax * kRowBytes;         // 1280: one plane image
 // the lo image sits an odd multiple of 64 bytes behind the hi image: the 8 lanes that file one 128-byte row (4 hi
 // chunks, 4 lo chunks) then cover all 32 store banks once
 constexpr int kLoOff = kPlaneBytes + 64;               // 1344
@@ -79,60 +78,6 @@ __device__ __forceinline__ float ds_scale(float own2, float other) {
   return plane_scale(2.f * __builtin_sqrtf(own2) * (kSqrtDh * other));
 }
 
-// ---- streamed tile pair: lane (r = lane >> 3, q = lane & 7) owns 16-byte chunk q (0..3: hi plane, 4..7: lo plane) of
-// pair-rows r + 8 i, i < 5; pair-rows 0..19 = tile A, 20..39 = tile B.  Strides in bytes.
-struct PairRegsP {
-  i32x4 v[5];
-};
-
-template <bool FULL, bool HALF>
-__device__ __forceinline__ void pair_load_p(PairRegsP &t, const char *baseA, unsigned strideA, const char *baseB,
-                                            unsigned strideB, int L, int lane) {
-  // dh = 32: 8 lanes per 128-byte slot row, 5 loads; HALF: 4 lanes per 64-byte slot row (chunks 0, 1 hi; 2, 3 lo), 3 loads
-  constexpr int LPR = HALF ? 4 : 8, RPL = 64 / LPR, NLD = HALF ? 3 : 5;
-  const int r = lane / LPR, q = lane % LPR;
-#pragma unroll
-  for (int i = 0; i < NLD; ++i) {
-    const int R = r + RPL * i;
-    const bool isB = R >= kLmax;
-    const int j = isB ? R - kLmax : R;
-    // per-lane part as a 32-bit byte offset on top of a tile base that is uniform per edge (base stays in SGPRs)
-    const unsigned off = (unsigned)j * (isB ? strideB : strideA) + 16u * (unsigned)q;
-    const char *p = (isB ? baseB : baseA) + off;
-    if (R < 2 * kLmax && (FULL || j < L)) t.v[i] = *reinterpret_cast<const i32x4 *>(p);
-  }
-}
-
-template <bool FULL, bool HALF>
-__device__ __forceinline__ void pair_to_lds_p(char *tileA, const PairRegsP &t, int L, int lane) {
-  constexpr int LPR = HALF ? 4 : 8, RPL = 64 / LPR, NLD = HALF ? 3 : 5, CPP = LPR / 2;      // chunks per plane
-  const int r = lane / LPR, q = lane % LPR;
-#pragma unroll
-  for (int i = 0; i < NLD; ++i) {
-    const int R = r + RPL * i;
-    const bool isB = R >= kLmax;
-    const int j = isB ? R - kLmax : R;
-    if (R < 2 * kLmax && (FULL || j < L))
-      *reinterpret_cast<i32x4 *>(tileA + (isB ? kTileBytes : 0) + (q >= CPP ? kLoOff : 0) + plane_off(j, q % CPP)) = t.v[i];
-  }
-}
-
-__device__ __forceinline__ void lds_zero(char *p, int bytes, int lane) {
-  int *z = reinterpret_cast<int *>(p);
-  for (int i = lane; i < bytes / 4; i += AMPCONV_WAVE) z[i] = 0;
-}
-
-// channel-product fragment (rowfrag: plane16.h, of ONE plane image) of column tile nt straight from global memory (the
-// unit's own side, once per unit; plain map: column m of tile 1 is token 16 + m; token rows >= L read as zero).
-// `base` = the row-0 slot of the (node, head), `plane` = 0 / 64
-template <bool HALF>
-__device__ __forceinline__ i32x4 rowfrag_global(const char *base, unsigned row_bytes, int nt, int plane, int L, int lane) {
-  const int m = lane & 15, kg = lane >> 4;
-  const int j = nt == 0 ? m : 16 + m;
-  i32x4 x = {0, 0, 0, 0};
-  if (j < L && (!HALF || kg < 2)) x = *reinterpret_cast<const i32x4 *>(base + (unsigned)j * row_bytes + plane + 16 * kg);
-  return x;
-}
 // C/D registers (already in the split's units, |x| < 2^16) -> the two planes of a token-product fragment: slots 0..3 =
 // t0 (tokens 4 g + q), slot 4 = t1_0 (token 16 + g), slots 5..7 zero
 __device__ __forceinline__ void cd_frag2(const f32x4 &t0, float t1_0, i32x4 &hi, i32x4 &lo) {
@@ -142,33 +87,6 @@ __device__ __forceinline__ void cd_frag2(const f32x4 &t0, float t1_0, i32x4 &hi,
   split2(t1_0, 0.f, h2, l2);
   hi = i32x4{h0, h1, h2, 0};
   lo = i32x4{l0, l1, l2, 0};
-}
-
-// softmax over the 20 source tokens of one destination-token column; `sc` = log2e / sqrt(dh) / (scale of Q' K'^T) is
-// applied to the raw scores here, the result leaves multiplied by `mul`.  t0[q] = token 4 g + q, t1[0] = token 16 + g
-// (regs 1..3 of tile 1 replicate it and come out as 0)
-// Returns m * sc + log2(sum): P = exp2(S' * sc - that), what the source pass needs to rebuild P without reducing again.
-template <bool FULL>
-__device__ __forceinline__ float column_softmax(f32x4 &t0, f32x4 &t1, float sc, float mul, int L, int g) {
-  if (!FULL) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if (4 * g + q >= L) t0[q] = kMasked;
-    if (16 + g >= L) t1[0] = kMasked;
-  }
-  float m = fmaxf(fmaxf(fmaxf(t0[0], t0[1]), fmaxf(t0[2], t0[3])), t1[0]);
-  m = groups_max(m);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) t0[q] = fast_exp2((t0[q] - m) * sc);
-  t1[0] = fast_exp2((t1[0] - m) * sc);
-  float l = ((t0[0] + t0[1]) + (t0[2] + t0[3])) + t1[0];
-  l = groups_sum(l);
-  const float inv = fast_rcp(l) * mul;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) t0[q] *= inv;
-  t1[0] *= inv;
-  t1[1] = t1[2] = t1[3] = 0.f;
-  return fmaf(m, sc, __builtin_amdgcn_logf(l));
 }
 
 struct Args {
@@ -185,10 +103,6 @@ struct Args {
   int64_t n_units;
   int L, H;
 };
-
-__device__ __forceinline__ const char *slot_ptr(const ampconv_view_t &v, int64_t n, int h) {
-  return reinterpret_cast<const char *>(v.ptr) + 4 * (n * v.node_stride + (int64_t)h * v.head_stride);
-}
 
 // output tile store (fp32): C/D layout lane (n = lane & 15, g), reg q -> channel 4 g + q + 16 mc, token of column n of
 // tile nt: n / 16 + n (plain map) or, QUARTER (the source pass's own tokens sit on quarter-mapped columns), 16 + (n >> 2)
@@ -215,210 +129,72 @@ __device__ __forceinline__ float store_tile(const ampconv_view_t &v, int64_t nod
   return m;
 }
 
-template <bool HALF>
-__device__ __forceinline__ void store_zero_tile(const ampconv_view_t &v, int64_t node, int h, int L, int lane) {
-  constexpr int MC = HALF ? 1 : 2;
-  f32x4 Z[MC][2];
-#pragma unroll
-  for (int mc = 0; mc < MC; ++mc) Z[mc][0] = Z[mc][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-  store_tile<false, MC>(v, node, h, Z, 0.f, L, lane);
-}
+// ---- the format: two fp16 planes (hi at 0, lo at kLoOff) of the scaled value, three products
+struct FmtP {
+  using Args = ::Args;
+  static constexpr int kPlanes = 2, kElemBytes = 4, kLoOff = ::kLoOff, kTileBytes = ::kTileBytes;
+  using Frag = wave16::Frag<2>;      // p[0] = hi, p[1] = lo
+  // dh = 32: 8 lanes per 128-byte slot row, 5 loads; HALF: 4 lanes per 64-byte slot row (chunks 0, 1 hi; 2, 3 lo), 3 loads.
+  // The registers are never touched for HALF: the images are zeroed once per unit instead
+  template <bool HALF> using Geom = PairGeom<HALF ? 4 : 8, HALF ? 3 : 5, HALF ? 4 : 8, 2, ::kLoOff>;
+  static constexpr bool kHalfZeroLds = true;
+  template <bool HALF> static constexpr int mc_tiles() { return HALF ? 1 : 2; }
+  // TR_PRE_READ in front of the transposed reads, the split of the softmax results in the shadow of those reads
+  static constexpr bool kShadow = true;
+  static constexpr float kMasked = ::kMasked, kPMul = kPScale;
 
-// ---------------------------------------------------------------- forward
-template <bool FULL, bool HALF>
-__global__ __launch_bounds__(64 * kWavesPerBlock, 4) void fwd_f16x2(Args a) {
-  constexpr int MC = HALF ? 1 : 2, kLo = HALF ? 32 : 64;          // channel tiles; byte offset of the lo plane in a slot
-  constexpr float kIs = HALF ? 0.25f : 0.17677669529663687f;     // 1 / sqrt(dh)
-  __shared__ __attribute__((aligned(16))) char lds_all[kWavesPerBlock][2 * kTileBytes];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t unit = (int64_t)blockIdx.x * kWavesPerBlock + wave;
-  if (unit >= a.n_units) return;
-  int64_t r, onode;
-  int h, beg, end, deg;
-  if (!map_unit(a.hub, a.ptr, unit, a.n_units, a.H, r, onode, h, beg, end, deg)) return;
-  if (beg >= end && a.hub.mode != 2) return store_zero_tile<HALF>(a.O, onode, h, a.L, lane);
-  const int L = a.L, g = lane >> 4;
-  char *Kt = lds_all[wave], *Vt = Kt + kTileBytes;
-  const float uq = 1.f / plane_scale(a.bounds[0]);           // exact: a power of two
-  const float sc = (kLog2e * kIs * uq) * uq;   // log2e / sqrt(32) / (scale of Q' K'^T)
-
-  i32x4 qh[2], ql[2];
-  {
-    const char *qb = slot_ptr(a.Q, r, h);
-    const unsigned rb = (unsigned)a.Q.row_stride * 4u;
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      qh[nt] = rowfrag_global<HALF>(qb, rb, nt, 0, L, lane);
-      ql[nt] = rowfrag_global<HALF>(qb, rb, nt, kLo, L, lane);
-    }
+  static __device__ __forceinline__ f32x4 mma(const Frag &a, const Frag &b, f32x4 c) { return mfma3(a.p[0], a.p[1], b.p[0], b.p[1], c); }
+  static __device__ __forceinline__ Frag cd_frag(const f32x4 &t0, const f32x4 &t1) {
+    Frag f;
+    cd_frag2(t0, t1[0], f.p[0], f.p[1]);
+    return f;
   }
-  if (!FULL || HALF) lds_zero(Kt, 2 * kTileBytes, lane);
-  f32x4 OT[MC][2];
-#pragma unroll
-  for (int mc = 0; mc < MC; ++mc) OT[mc][0] = OT[mc][1] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  PairRegsP kv;
-  IdxWindow win;
-  const unsigned krb = (unsigned)a.K.row_stride * 4u, vrb = (unsigned)a.V.row_stride * 4u;
-  auto fetch = [&](int p) {
-    const int64_t s = idxwin_get<false>(win, a.idx, nullptr, p, end, lane, nullptr);
-    pair_load_p<FULL, HALF>(kv, slot_ptr(a.K, s, h), krb, slot_ptr(a.V, s, h), vrb, L, lane);
+  // scales: the planes' power-of-two scales are undone in the exponent (uq^2) and at the stores, softmax weights travel
+  // as P * kPScale, dS in the unit's own split scale; dObar arrives divided by the in-degree, so 1/deg enters nowhere
+  // but the forward mean
+  struct Scales {
+    float uq, ug, sc;      // 1 / scale of Q|K|V, 1 / scale of dObar (exact: powers of two), log2e / sqrt(dh) / (scale of Q' K'^T)
   };
-  if (beg < end) {
-    idxwin_load<false>(win, a.idx, nullptr, beg, end, lane);
-    fetch(beg);
+  template <bool HALF> static constexpr float inv_sqrt_dh() { return HALF ? 0.25f : 0.17677669529663687f; }
+  template <bool HALF> static __device__ __forceinline__ Scales scales(const Args &a) {
+    const float uq = 1.f / plane_scale(uniform_ld(a.bounds)), ug = 1.f / plane_scale(uniform_ld(a.bounds + 1));
+    return Scales{uq, ug, (kLog2e * inv_sqrt_dh<HALF>() * uq) * uq};
   }
-  for (int p = beg; p < end; ++p) {
-    pair_to_lds_p<FULL, HALF>(Kt, kv, L, lane);
-    if (p + 1 < end) fetch(p + 1);
-    __builtin_amdgcn_wave_barrier();
-
-    f32x4 S[2][2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      const i32x4 kh = rowfrag(Kt, mt, lane), kl = rowfrag(Kt + kLoOff, mt, lane);
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) S[mt][nt] = mfma3(kh, kl, qh[nt], ql[nt], f32x4{0.f, 0.f, 0.f, 0.f});
-    }
-    i32x4 ph[2], pl[2];
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) column_softmax<FULL>(S[0][nt], S[1][nt], sc, kPScale, L, g);
-    i32x4 vh[MC], vl[MC];
-    TR_PRE_READ();
-#pragma unroll
-    for (int mc = 0; mc < MC; ++mc) {
-      vh[mc] = colfrag(Vt, mc, lane);
-      vl[mc] = colfrag(Vt + kLoOff, mc, lane);
-    }
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) cd_frag2(S[0][nt], S[1][nt][0], ph[nt], pl[nt]);      // (in the shadow of the reads)
-    TR_FRAG_FENCE();
-#pragma unroll
-    for (int mc = 0; mc < MC; ++mc)
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) OT[mc][nt] = mfma3(vh[mc], vl[mc], ph[nt], pl[nt], OT[mc][nt]);
-    __builtin_amdgcn_wave_barrier();
-  }
-  const bool hubp = a.hub.mode == 2;
-  store_tile<false, MC>(a.O, onode, h, OT, kPUnscale * uq * (hubp ? 1.f : (deg > 0 ? 1.f / (float)deg : 0.f)), L, lane);
-}
-
-// ---------------------------------------------------------------- backward, destination pass
-template <bool FULL, bool STATS, bool HALF>
-__global__ __launch_bounds__(64 * kWavesPerBlock, 3) void bwd_dst_f16x2(Args a) {
-  constexpr int MC = HALF ? 1 : 2, kLo = HALF ? 32 : 64;
-  constexpr float kIs = HALF ? 0.25f : 0.17677669529663687f;
-  __shared__ __attribute__((aligned(16))) char lds_all[kWavesPerBlock][2 * kTileBytes];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t unit = (int64_t)blockIdx.x * kWavesPerBlock + wave;
-  if (unit >= a.n_units) return;
-  int64_t r, onode;
-  int h, beg, end, deg;
-  if (!map_unit(a.hub, a.ptr, unit, a.n_units, a.H, r, onode, h, beg, end, deg)) return;
-  if (beg >= end && a.hub.mode != 2) return store_zero_tile<HALF>(a.O, onode, h, a.L, lane);
-  const int L = a.L, g = lane >> 4;
-  char *Kt = lds_all[wave], *Vt = Kt + kTileBytes;
-  const float uq = 1.f / plane_scale(a.bounds[0]), ug = 1.f / plane_scale(a.bounds[1]);
-  const float sc = (kLog2e * kIs * uq) * uq;
-
-  i32x4 qh[2], ql[2], gh[2], gl[2];
-  {
-    const char *qb = slot_ptr(a.Q, r, h), *gb = slot_ptr(a.dO, r, h);
-    const unsigned qrb = (unsigned)a.Q.row_stride * 4u, grb = (unsigned)a.dO.row_stride * 4u;
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      qh[nt] = rowfrag_global<HALF>(qb, qrb, nt, 0, L, lane);
-      ql[nt] = rowfrag_global<HALF>(qb, qrb, nt, kLo, L, lane);
-      gh[nt] = rowfrag_global<HALF>(gb, grb, nt, 0, L, lane);
-      gl[nt] = rowfrag_global<HALF>(gb, grb, nt, kLo, L, lane);
-    }
-  }
+  static __device__ __forceinline__ int64_t qrow(const Args &, int64_t r) { return r; }
+  static __device__ __forceinline__ float fwd_scale(const Scales &k, float mean) { return kPUnscale * k.uq * mean; }
   // dS scale of this unit: its own dObar rows against the bound of any V row
-  const float ss = ds_scale(tile_max_norm2(gh[0], gh[1]), a.bounds[2] * plane_scale(a.bounds[0]));
-  if (!FULL || HALF) lds_zero(Kt, 2 * kTileBytes, lane);
-  f32x4 dQT[MC][2];
-#pragma unroll
-  for (int mc = 0; mc < MC; ++mc) dQT[mc][0] = dQT[mc][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  PairRegsP kv;
-  IdxWindow win;
-  const unsigned krb = (unsigned)a.K.row_stride * 4u, vrb = (unsigned)a.V.row_stride * 4u;
-  // (STATS: the window's weight slot carries the bits of spos[p], the CSC position of the edge)
-  const float *sposf = reinterpret_cast<const float *>(a.spos);
-  float cposf = 0.f, cposf_next = 0.f;
-  auto fetch = [&](int p) {
-    const int64_t s = idxwin_get<STATS>(win, a.idx, sposf, p, end, lane, &cposf_next);
-    pair_load_p<FULL, HALF>(kv, slot_ptr(a.K, s, h), krb, slot_ptr(a.V, s, h), vrb, L, lane);
-  };
-  if (beg < end) {
-    idxwin_load<STATS>(win, a.idx, sposf, beg, end, lane);
-    fetch(beg);
+  static __device__ __forceinline__ float ds_mul(const Args &a, int, const Frag (&gB)[2]) {
+    return ds_scale(tile_max_norm2(gB[0].p[0], gB[1].p[0]), uniform_ld(a.bounds + 2) * plane_scale(uniform_ld(a.bounds)));
   }
-  for (int p = beg; p < end; ++p) {
-    pair_to_lds_p<FULL, HALF>(Kt, kv, L, lane);
-    cposf = cposf_next;
-    if (p + 1 < end) fetch(p + 1);
-    __builtin_amdgcn_wave_barrier();
-
-    f32x4 S[2][2], dP[2][2];
-    float lse[2], dlt[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      const i32x4 kh = rowfrag(Kt, mt, lane), kl = rowfrag(Kt + kLoOff, mt, lane);
-      const i32x4 vh = rowfrag(Vt, mt, lane), vl = rowfrag(Vt + kLoOff, mt, lane);
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        S[mt][nt] = mfma3(kh, kl, qh[nt], ql[nt], f32x4{0.f, 0.f, 0.f, 0.f});
-        dP[mt][nt] = mfma3(vh, vl, gh[nt], gl[nt], f32x4{0.f, 0.f, 0.f, 0.f});
-      }
-    }
-    i32x4 sh[2], sl[2];
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      lse[nt] = column_softmax<FULL>(S[0][nt], S[1][nt], sc, 1.f, L, g);        // P^T; tile-1 regs 1..3 come out 0
-      float part = S[1][nt][0] * dP[1][nt][0];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) part = fmaf(S[0][nt][q], dP[0][nt][q], part);
-      const float delta = groups_sum(part);
-      dlt[nt] = delta;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) S[0][nt][q] *= (dP[0][nt][q] - delta) * ss;      // dS^T in the unit's split scale
-      S[1][nt][0] *= (dP[1][nt][0] - delta) * ss;
-    }
-    i32x4 ch[MC], cl[MC];
-    TR_PRE_READ();
-#pragma unroll
-    for (int mc = 0; mc < MC; ++mc) {
-      ch[mc] = colfrag(Kt, mc, lane);
-      cl[mc] = colfrag(Kt + kLoOff, mc, lane);
-    }
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) cd_frag2(S[0][nt], S[1][nt][0], sh[nt], sl[nt]);
-    TR_FRAG_FENCE();
-#pragma unroll
-    for (int mc = 0; mc < MC; ++mc)
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) dQT[mc][nt] = mfma3(ch[mc], cl[mc], sh[nt], sl[nt], dQT[mc][nt]);
-    if (STATS) {
-      // every lane group holds the statistics of its column: lanes 0..15 have tokens 0..15 (tile 0), lanes 16..19
-      // (group 1, columns 0..3) tokens 16..19 (tile 1): two 80-byte stores per edge and head
-      float *st = a.stats + ((int64_t)__builtin_bit_cast(int, cposf) * a.H + h) * kStatsPerUnit;
-      if (lane < L) {
-        st[lane] = lane < 16 ? lse[0] : lse[1];
-        st[kLmax + lane] = lane < 16 ? dlt[0] : dlt[1];
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
+  // dQ = sum dS K / sqrt(dh): undo the split scale, the scales of dP' (Q|K|V and dObar) and of K'
+  template <bool HALF> static __device__ __forceinline__ float dq_scale(const Args &, const Scales &k, float ss, bool hubp) {
+    return (((1.f / ss) * k.uq) * k.ug) * k.uq * (hubp ? 1.f : inv_sqrt_dh<HALF>());
   }
-  // dQ = sum dS K / sqrt(dh): undo the split scale, the scales of dP' (Q|K|V and dObar) and of K'; the hub pass leaves
-  // 1/sqrt(dh) to the combine pass
-  const bool hubp = a.hub.mode == 2;
-  const float m = store_tile<false, MC>(a.O, onode, h, dQT, (((1.f / ss) * uq) * ug) * uq * (hubp ? 1.f : kIs),
-                                    L, lane);
-  if (a.absmax) wave_record_absmax(a.absmax, m);
-}
+
+  // fp32 (the hub pass's partial tiles are fp32 too); returns the largest finite magnitude stored
+  template <bool HALF>
+  static __device__ __forceinline__ float store(const ampconv_view_t &v, int64_t node, int h, const f32x4 (&T)[HALF ? 1 : 2][2],
+                                                float scale, bool, int L, int lane) {
+    return store_tile<false, HALF ? 1 : 2>(v, node, h, T, scale, L, lane);
+  }
+  template <bool HALF>
+  static __device__ __forceinline__ void store_zero(const ampconv_view_t &v, int64_t node, int h, int L, int lane) {
+    constexpr int MC = HALF ? 1 : 2;
+    f32x4 Z[MC][2];
+#pragma unroll
+    for (int mc = 0; mc < MC; ++mc) Z[mc][0] = Z[mc][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    store_tile<false, MC>(v, node, h, Z, 0.f, L, lane);
+  }
+  static __device__ __forceinline__ void record_absmax(const Args &a, float m) {
+    if (a.absmax) wave_record_absmax(a.absmax, m);
+  }
+};
+
+template <bool FULL, bool HALF>
+__global__ __launch_bounds__(64 * kWavesPerBlock, 4) void fwd_f16x2(Args a) { fwd_body<FmtP, FULL, HALF>(a); }
+template <bool FULL, bool STATS, bool HALF>
+__global__ __launch_bounds__(64 * kWavesPerBlock, 3) void bwd_dst_f16x2(Args a) { bwd_dst_body<FmtP, FULL, STATS, HALF>(a); }
 
 // ---------------------------------------------------------------- backward, source pass
 // The unit's OWN K / V tiles live in two more LDS images and are re-read per edge (the registers they would occupy are
@@ -428,187 +204,170 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 3) void bwd_dst_f16x2(Args a) 
 constexpr int kSrcLds = 4 * kTileBytes + 2 * kLmax * 4 + 32;      // four tile images + the edge's statistics (padded to 16)
 template <bool FULL, bool STATS, bool HALF>
 __global__ __launch_bounds__(64 * kWavesPerBlock, 3) void bwd_src_f16x2(Args a) {
+  using G = FmtP::Geom<HALF>;
   constexpr int MC = HALF ? 1 : 2;
-  constexpr float kIs = HALF ? 0.25f : 0.17677669529663687f;
   __shared__ __attribute__((aligned(16))) char lds_all[kWavesPerBlock][kSrcLds];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t unit = (int64_t)blockIdx.x * kWavesPerBlock + wave;
-  if (unit >= a.n_units) return;
-  int64_t s, onode;
-  int h, beg, end, deg;
-  if (!map_unit(a.hub, a.ptr, unit, a.n_units, a.H, s, onode, h, beg, end, deg)) return;
-  if (beg >= end && a.hub.mode != 2) {
-    store_zero_tile<HALF>(a.dK, onode, h, a.L, lane);
-    return store_zero_tile<HALF>(a.dV, onode, h, a.L, lane);
-  }
-  const int L = a.L, n = lane & 15;
-  char *Qt = lds_all[wave], *Gt = Qt + kTileBytes, *Ko = Gt + kTileBytes, *Vo = Ko + kTileBytes;
-  const float uq = 1.f / plane_scale(a.bounds[0]), ug = 1.f / plane_scale(a.bounds[1]);
-  const float sc = (kLog2e * kIs * uq) * uq;
+  for_unit<FmtP, HALF>(a, a.dK, &a.dV, [&](const Unit &u) __attribute__((always_inline)) {
+    const int lane = u.lane, h = u.h, beg = u.beg, end = u.end;
+    const int L = a.L, n = lane & 15;
+    char *Qt = lds_all[u.wave], *Gt = Qt + kTileBytes, *Ko = Gt + kTileBytes, *Vo = Ko + kTileBytes;
+    const FmtP::Scales k = FmtP::scales<HALF>(a);
+    const float ug = k.ug, sc = k.sc;
 
-  if (!FULL || HALF) lds_zero(Qt, 4 * kTileBytes, lane);
-  PairRegsP qg;
-  pair_load_p<FULL, HALF>(qg, slot_ptr(a.K, s, h), (unsigned)a.K.row_stride * 4u, slot_ptr(a.V, s, h),
-                    (unsigned)a.V.row_stride * 4u, L, lane);
-  pair_to_lds_p<FULL, HALF>(Ko, qg, L, lane);
-  __builtin_amdgcn_wave_barrier();
-  // dS scale of this unit: its own V rows against the bound of any dObar row
-  const float ss = ds_scale(tile_max_norm2(rowfrag(Vo, 0, lane), rowfrag(Vo, 1, lane)), a.bounds[3] * plane_scale(a.bounds[1]));
-  f32x4 dKT[MC][2], dVT[MC][2];
-#pragma unroll
-  for (int mc = 0; mc < MC; ++mc)
-    dKT[mc][0] = dKT[mc][1] = dVT[mc][0] = dVT[mc][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  IdxWindow win;
-  const unsigned qrb = (unsigned)a.Q.row_stride * 4u, grb = (unsigned)a.dO.row_stride * 4u;
-  float *stl = reinterpret_cast<float *>(Vo + kTileBytes);      // the edge's 40 statistics, staged for the row reads
-  float sv = 0.f;                                               // lane l < 40: statistic l of the edge in flight
-  auto fetch = [&](int p) {
-    const int64_t d = idxwin_get<false>(win, a.idx, nullptr, p, end, lane, nullptr);
-    pair_load_p<FULL, HALF>(qg, slot_ptr(a.Q, d, h), qrb, slot_ptr(a.dO, d, h), grb, L, lane);
-    if (STATS && lane < kStatsPerUnit) sv = a.stats[((int64_t)p * a.H + h) * kStatsPerUnit + lane];
-  };
-  if (beg < end) {
-    idxwin_load<false>(win, a.idx, nullptr, beg, end, lane);
-    fetch(beg);
-  }
-  // own tokens on the columns: tile 0 column n = token n, tile 1 column n = token 16 + (n >> 2), one lane per token
-  const bool v0 = FULL || n < L, v1 = (n & 3) == 0 && 16 + (n >> 2) < L;
-  for (int p = beg; p < end; ++p) {
-    pair_to_lds_p<FULL, HALF>(Qt, qg, L, lane);
-    if (STATS && lane < kStatsPerUnit) stl[lane] = sv;
-    if (p + 1 < end) fetch(p + 1);
+    if (!FULL || HALF) lds_zero(Qt, 4 * kTileBytes, lane);
+    Pair16<G::NLD> qg;
+    pair16_load<FULL, G>(qg, slot_ptr<4>(a.K, u.row, h), (unsigned)a.K.row_stride * 4u, slot_ptr<4>(a.V, u.row, h),
+                       (unsigned)a.V.row_stride * 4u, L, lane);
+    pair16_to_lds<FULL, G, kTileBytes>(Ko, qg, L, lane);
     __builtin_amdgcn_wave_barrier();
+    // dS scale of this unit: its own V rows against the bound of any dObar row
+    const float ss = ds_scale(tile_max_norm2(rowfrag(Vo, 0, lane), rowfrag(Vo, 1, lane)), uniform_ld(a.bounds + 3) * plane_scale(uniform_ld(a.bounds + 1)));
+    f32x4 dKT[MC][2], dVT[MC][2];
+#pragma unroll
+    for (int mc = 0; mc < MC; ++mc)
+      dKT[mc][0] = dKT[mc][1] = dVT[mc][0] = dVT[mc][1] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    f32x4 S[2][2], dP[2][2];
-    {
-      i32x4 kh[2], kl[2], vh[2], vl[2];
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        kh[nt] = rowfrag(Ko, nt, lane);
-        kl[nt] = rowfrag(Ko + kLoOff, nt, lane);
-        vh[nt] = rowfrag(Vo, nt, lane);
-        vl[nt] = rowfrag(Vo + kLoOff, nt, lane);
-      }
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        const i32x4 ah = rowfrag(Qt, mt, lane), al = rowfrag(Qt + kLoOff, mt, lane);
-        const i32x4 bh = rowfrag(Gt, mt, lane), bl = rowfrag(Gt + kLoOff, mt, lane);
+    IdxWindow win;
+    const unsigned qrb = (unsigned)a.Q.row_stride * 4u, grb = (unsigned)a.dO.row_stride * 4u;
+    float *stl = reinterpret_cast<float *>(Vo + kTileBytes);      // the edge's 40 statistics, staged for the row reads
+    float sv = 0.f;                                               // lane l < 40: statistic l of the edge in flight
+    auto fetch = [&](int p) {
+      const int64_t d = idxwin_get<false>(win, a.idx, nullptr, p, end, lane, nullptr);
+      pair16_load<FULL, G>(qg, slot_ptr<4>(a.Q, d, h), qrb, slot_ptr<4>(a.dO, d, h), grb, L, lane);
+      if (STATS && lane < kStatsPerUnit) sv = a.stats[((int64_t)p * a.H + h) * kStatsPerUnit + lane];
+    };
+    if (beg < end) {
+      idxwin_load<false>(win, a.idx, nullptr, beg, end, lane);
+      fetch(beg);
+    }
+    // own tokens on the columns: tile 0 column n = token n, tile 1 column n = token 16 + (n >> 2), one lane per token
+    const bool v0 = FULL || n < L, v1 = (n & 3) == 0 && 16 + (n >> 2) < L;
+    for (int p = beg; p < end; ++p) {
+      pair16_to_lds<FULL, G, kTileBytes>(Qt, qg, L, lane);
+      if (STATS && lane < kStatsPerUnit) stl[lane] = sv;
+      if (p + 1 < end) fetch(p + 1);
+      __builtin_amdgcn_wave_barrier();
+
+      f32x4 S[2][2], dP[2][2];
+      {
+        i32x4 kh[2], kl[2], vh[2], vl[2];
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
-          S[mt][nt] = mfma3(ah, al, kh[nt], kl[nt], f32x4{0.f, 0.f, 0.f, 0.f});
-          dP[mt][nt] = mfma3(bh, bl, vh[nt], vl[nt], f32x4{0.f, 0.f, 0.f, 0.f});
+          kh[nt] = rowfrag(Ko, nt, lane);
+          kl[nt] = rowfrag(Ko + kLoOff, nt, lane);
+          vh[nt] = rowfrag(Vo, nt, lane);
+          vl[nt] = rowfrag(Vo + kLoOff, nt, lane);
+        }
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+          const i32x4 ah = rowfrag(Qt, mt, lane), al = rowfrag(Qt + kLoOff, mt, lane);
+          const i32x4 bh = rowfrag(Gt, mt, lane), bl = rowfrag(Gt + kLoOff, mt, lane);
+#pragma unroll
+          for (int nt = 0; nt < 2; ++nt) {
+            S[mt][nt] = mfma3(ah, al, kh[nt], kl[nt], f32x4{0.f, 0.f, 0.f, 0.f});
+            dP[mt][nt] = mfma3(bh, bl, vh[nt], vl[nt], f32x4{0.f, 0.f, 0.f, 0.f});
+          }
         }
       }
-    }
-    // row softmax over the source tokens (columns across the 16 lanes of a DPP row); rows: tile 0 reg q = destination
-    // token 4 g + q, tile 1 reg 0 = token 16 + g (quarter map).  After this block S holds P * 2^14 (for dV) and dP holds
-    // dS in the unit's split scale.
-    if (STATS) {
-      // element-wise with the statistics of the destination pass: rows of tile 0 = tokens 4 g .. 4 g + 3, tile 1 reg 0 =
-      // token 16 + g
-      const int g = lane >> 4;
-      const f32x4 l0 = *reinterpret_cast<const f32x4 *>(stl + 4 * g), d0 = *reinterpret_cast<const f32x4 *>(stl + kLmax + 4 * g);
-      const float l1 = stl[16 + g], d1 = stl[kLmax + 16 + g];
+      // row softmax over the source tokens (columns across the 16 lanes of a DPP row); rows: tile 0 reg q = destination
+      // token 4 g + q, tile 1 reg 0 = token 16 + g (quarter map).  After this block S holds P * 2^14 (for dV) and dP holds
+      // dS in the unit's split scale.
+      if (STATS) {
+        // element-wise with the statistics of the destination pass: rows of tile 0 = tokens 4 g .. 4 g + 3, tile 1 reg 0 =
+        // token 16 + g
+        const int g = lane >> 4;
+        const f32x4 l0 = *reinterpret_cast<const f32x4 *>(stl + 4 * g), d0 = *reinterpret_cast<const f32x4 *>(stl + kLmax + 4 * g);
+        const float l1 = stl[16 + g], d1 = stl[kLmax + 16 + g];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+#pragma unroll
+          for (int q = 0; q < (mt == 0 ? 4 : 1); ++q) {
+            // (rows of tokens >= L have no statistics: their weights are zero, not exp2 of whatever the buffer holds --
+            // which the destination pass never wrote and may be a NaN or an infinity, so it is not read into ls / dl)
+            const bool vr = FULL || (mt == 0 ? 4 * g + q : 16 + g) < L;
+            const float ls = !vr ? 0.f : mt == 0 ? l0[q] : l1, dl = !vr ? 0.f : mt == 0 ? d0[q] : d1;
+            const float s0 = (v0 && vr) ? S[mt][0][q] : kMasked, s1 = (v1 && vr) ? S[mt][1][q] : kMasked;
+            const float p0 = fast_exp2(fmaf(s0, sc, -ls)), p1 = fast_exp2(fmaf(s1, sc, -ls));
+            S[mt][0][q] = p0 * kPScale;
+            S[mt][1][q] = p1 * kPScale;
+            dP[mt][0][q] = p0 * (dP[mt][0][q] - dl) * ss;
+            dP[mt][1][q] = p1 * (dP[mt][1][q] - dl) * ss;
+          }
+        }
+      } else {
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) {
 #pragma unroll
         for (int q = 0; q < (mt == 0 ? 4 : 1); ++q) {
-          // (rows of tokens >= L have no statistics: their weights are zero, not exp2 of whatever the buffer holds --
-          // which the destination pass never wrote and may be a NaN or an infinity, so it is not read into ls / dl)
-          const bool vr = FULL || (mt == 0 ? 4 * g + q : 16 + g) < L;
-          const float ls = !vr ? 0.f : mt == 0 ? l0[q] : l1, dl = !vr ? 0.f : mt == 0 ? d0[q] : d1;
-          const float s0 = (v0 && vr) ? S[mt][0][q] : kMasked, s1 = (v1 && vr) ? S[mt][1][q] : kMasked;
-          const float p0 = fast_exp2(fmaf(s0, sc, -ls)), p1 = fast_exp2(fmaf(s1, sc, -ls));
+          const float s0 = v0 ? S[mt][0][q] : kMasked, s1 = v1 ? S[mt][1][q] : kMasked;
+          const float m = row16_max(fmaxf(s0, s1));
+          float p0 = fast_exp2((s0 - m) * sc), p1 = fast_exp2((s1 - m) * sc);
+          const float rinv = fast_rcp(row16_sum(p0 + p1));
+          p0 *= rinv;
+          p1 *= rinv;
+          const float delta = row16_sum(fmaf(p0, dP[mt][0][q], p1 * dP[mt][1][q]));
           S[mt][0][q] = p0 * kPScale;
           S[mt][1][q] = p1 * kPScale;
-          dP[mt][0][q] = p0 * (dP[mt][0][q] - dl) * ss;
-          dP[mt][1][q] = p1 * (dP[mt][1][q] - dl) * ss;
+          dP[mt][0][q] = p0 * (dP[mt][0][q] - delta) * ss;
+          dP[mt][1][q] = p1 * (dP[mt][1][q] - delta) * ss;
         }
       }
-    } else {
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-      for (int q = 0; q < (mt == 0 ? 4 : 1); ++q) {
-        const float s0 = v0 ? S[mt][0][q] : kMasked, s1 = v1 ? S[mt][1][q] : kMasked;
-        const float m = row16_max(fmaxf(s0, s1));
-        float p0 = fast_exp2((s0 - m) * sc), p1 = fast_exp2((s1 - m) * sc);
-        const float rinv = fast_rcp(row16_sum(p0 + p1));
-        p0 *= rinv;
-        p1 *= rinv;
-        const float delta = row16_sum(fmaf(p0, dP[mt][0][q], p1 * dP[mt][1][q]));
-        S[mt][0][q] = p0 * kPScale;
-        S[mt][1][q] = p1 * kPScale;
-        dP[mt][0][q] = p0 * (dP[mt][0][q] - delta) * ss;
-        dP[mt][1][q] = p1 * (dP[mt][1][q] - delta) * ss;
       }
-    }
-    }
-    {
-      i32x4 ph[2], pl[2], gh[MC], gl[MC];
-      TR_PRE_READ();
+      {
+        i32x4 ph[2], pl[2], gh[MC], gl[MC];
+        TR_PRE_READ();
 #pragma unroll
-      for (int mc = 0; mc < MC; ++mc) {
-        gh[mc] = colfrag(Gt, mc, lane);
-        gl[mc] = colfrag(Gt + kLoOff, mc, lane);
+        for (int mc = 0; mc < MC; ++mc) {
+          gh[mc] = colfrag(Gt, mc, lane);
+          gl[mc] = colfrag(Gt + kLoOff, mc, lane);
+        }
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) cd_frag2(S[0][nt], S[1][nt][0], ph[nt], pl[nt]);
+        TR_FRAG_FENCE();
+#pragma unroll
+        for (int mc = 0; mc < MC; ++mc)
+#pragma unroll
+          for (int nt = 0; nt < 2; ++nt) dVT[mc][nt] = mfma3(gh[mc], gl[mc], ph[nt], pl[nt], dVT[mc][nt]);
+        TR_WAR_GUARD();
       }
+      {
+        i32x4 sh[2], sl[2], qh[MC], ql[MC];
 #pragma unroll
-      for (int nt = 0; nt < 2; ++nt) cd_frag2(S[0][nt], S[1][nt][0], ph[nt], pl[nt]);
-      TR_FRAG_FENCE();
+        for (int mc = 0; mc < MC; ++mc) {
+          qh[mc] = colfrag(Qt, mc, lane);
+          ql[mc] = colfrag(Qt + kLoOff, mc, lane);
+        }
 #pragma unroll
-      for (int mc = 0; mc < MC; ++mc)
+        for (int nt = 0; nt < 2; ++nt) cd_frag2(dP[0][nt], dP[1][nt][0], sh[nt], sl[nt]);
+        TR_FRAG_FENCE();
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt) dVT[mc][nt] = mfma3(gh[mc], gl[mc], ph[nt], pl[nt], dVT[mc][nt]);
-      TR_WAR_GUARD();
-    }
-    {
-      i32x4 sh[2], sl[2], qh[MC], ql[MC];
+        for (int mc = 0; mc < MC; ++mc)
 #pragma unroll
-      for (int mc = 0; mc < MC; ++mc) {
-        qh[mc] = colfrag(Qt, mc, lane);
-        ql[mc] = colfrag(Qt + kLoOff, mc, lane);
+          for (int nt = 0; nt < 2; ++nt) dKT[mc][nt] = mfma3(qh[mc], ql[mc], sh[nt], sl[nt], dKT[mc][nt]);
       }
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) cd_frag2(dP[0][nt], dP[1][nt][0], sh[nt], sl[nt]);
-      TR_FRAG_FENCE();
-#pragma unroll
-      for (int mc = 0; mc < MC; ++mc)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) dKT[mc][nt] = mfma3(qh[mc], ql[mc], sh[nt], sl[nt], dKT[mc][nt]);
+      __builtin_amdgcn_wave_barrier();
     }
-    __builtin_amdgcn_wave_barrier();
-  }
-  // dK = sum dS^T Q / sqrt(dh), dV = sum P^T dObar (1/deg is inside dObar); the hub pass leaves 1/sqrt(dh) to the combine
-  const bool hubp = a.hub.mode == 2;
-  float m = store_tile<true, MC>(a.dK, onode, h, dKT, (((1.f / ss) * uq) * ug) * uq * (hubp ? 1.f : kIs), L, lane);
-  m = fmaxf(m, store_tile<true, MC>(a.dV, onode, h, dVT, kPUnscale * ug, L, lane));
-  if (a.absmax) wave_record_absmax(a.absmax, m);
+    // dK = sum dS^T Q / sqrt(dh), dV = sum P^T dObar (1/deg is inside dObar); the hub pass leaves 1/sqrt(dh) to the combine
+    const bool hubp = a.hub.mode == 2;
+    float m = store_tile<true, MC>(a.dK, u.onode, h, dKT, FmtP::dq_scale<HALF>(a, k, ss, hubp), L, lane);
+    m = fmaxf(m, store_tile<true, MC>(a.dV, u.onode, h, dVT, kPUnscale * ug, L, lane));
+    FmtP::record_absmax(a, m);
+  });
 }
 
 typedef void (*EdgeKernel)(Args);
-// kernels[2 * half + full]
-int launch(Args &a, int L, bool half, EdgeKernel const (&kernels)[4], hipStream_t stream) {
-  return launch_wave_units(kernels[2 * half + (L == kLmax)], a, kWavesPerBlock, stream);
-}
+// kernels[stats][half][full]
 int launch_fwd(Args &a, int L, bool half, hipStream_t st) {
-  static const EdgeKernel k[4] = {fwd_f16x2<false, false>, fwd_f16x2<true, false>, fwd_f16x2<false, true>, fwd_f16x2<true, true>};
-  return launch(a, L, half, k, st);
+  static const EdgeKernel k[2][2] = WAVE16_KERNELS(fwd_f16x2);
+  return launch_wave16(k, a, L, half, st);
 }
 int launch_dst(Args &a, int L, bool half, hipStream_t st) {
-  static const EdgeKernel ks[4] = {bwd_dst_f16x2<false, true, false>, bwd_dst_f16x2<true, true, false>,
-                                   bwd_dst_f16x2<false, true, true>, bwd_dst_f16x2<true, true, true>};
-  static const EdgeKernel kn[4] = {bwd_dst_f16x2<false, false, false>, bwd_dst_f16x2<true, false, false>,
-                                   bwd_dst_f16x2<false, false, true>, bwd_dst_f16x2<true, false, true>};
-  return a.stats ? launch(a, L, half, ks, st) : launch(a, L, half, kn, st);
+  static const EdgeKernel k[2][2][2] = {WAVE16_KERNELS_STATS(bwd_dst_f16x2, false), WAVE16_KERNELS_STATS(bwd_dst_f16x2, true)};
+  return launch_wave16(k[a.stats != nullptr], a, L, half, st);
 }
 int launch_src(Args &a, int L, bool half, hipStream_t st) {
-  static const EdgeKernel ks[4] = {bwd_src_f16x2<false, true, false>, bwd_src_f16x2<true, true, false>,
-                                   bwd_src_f16x2<false, true, true>, bwd_src_f16x2<true, true, true>};
-  static const EdgeKernel kn[4] = {bwd_src_f16x2<false, false, false>, bwd_src_f16x2<true, false, false>,
-                                   bwd_src_f16x2<false, false, true>, bwd_src_f16x2<true, false, true>};
-  return a.stats ? launch(a, L, half, ks, st) : launch(a, L, half, kn, st);
+  static const EdgeKernel k[2][2][2] = {WAVE16_KERNELS_STATS(bwd_src_f16x2, false), WAVE16_KERNELS_STATS(bwd_src_f16x2, true)};
+  return launch_wave16(k[a.stats != nullptr], a, L, half, st);
 }
 
 // planes: 16-byte aligned, the head's dh channels one 4 dh-byte slot, rows a whole number of 16-byte pieces apart
