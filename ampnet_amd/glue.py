@@ -177,6 +177,10 @@ class ActDropout(_SeededSite):
     def forward(self, x):
         return act_dropout(x, self.p, self.activation, self.training, self._next_seed())
 
+    def activate(self, x):
+        """The site with dropout off, whatever `training` says; advances no counter."""
+        return act_dropout(x, 0.0, self.activation, False)
+
     def extra_repr(self):
         return f'p={self.p}, activation={self.activation!r}'
 
@@ -192,6 +196,10 @@ class TokenReadout(_SeededSite):
     def forward(self, x):
         return act_dropout_pool(x, self.embed_dim, self.p, self.activation, self.pooling, self.training,
                                 self._next_seed())
+
+    def activate(self, x):
+        """The site with dropout off and without the pooling: [N, L * embed_dim]; advances no counter."""
+        return act_dropout(x, 0.0, self.activation, False)
 
     def extra_repr(self):
         return f'embed_dim={self.embed_dim}, p={self.p}, activation={self.activation!r}, pooling={self.pooling!r}'

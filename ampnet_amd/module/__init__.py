@@ -1,4 +1,5 @@
-from .amp_gcn import AMPGCN, FeatureTokens
+from .amp_gcn import AMPGCN
+from .feature_tokens import FeatureTokens
 from .gcn import GCN
 
 __all__ = ['AMPGCN', 'FeatureTokens', 'GCN']

@@ -1,21 +1,30 @@
-"""AMPGCN on MI355X: the reference's 2-layer model around AMPConv with its featuriser on the device.
+"""AMPGCN on MI355X: the reference's 2-layer model around AMPConv, with its featuriser on the device.
 
-Mirrors reference src/ampnet/module/amp_gcn.py:20-118 (constructor arguments, sub-module names and
-therefore state-dict keys: feature_embedding_table, conv1, conv2, final_linear_out) and :239-276
-(forward: dropout_adj -> featurise -> conv1 -> ReLU -> conv2 -> ReLU -> token pooling -> Linear
--> log_softmax; `fused_glue=True` runs the dropouts, activations and the pooling between those as fused HIP passes,
-`fused_head=True` the Linear and the log_softmax / sigmoid as one more, and `nll_loss` the training loss behind them;
-`layer_norm=True` adds the per-token LayerNorm sites norm1, norm2 of experiments/cora_overfit_one_subgraph.py:46-107).  Both featuriser branches of :120-183 are here: down-sampling of the present features
-(:127-153, the Cora harness) and the full-width branch (:170-181, `downsample_feature_vectors=False`,
-the XOR harness of synthetic_benchmark/xor_training_utils.py:58-72); both poolings of :268-271 (token mean,
-or token 0 with `average_pooling_flag=False`).  The gradient and activation diagnostics of :278-405 (plot_grad_flow,
-visualize_gradients, visualize_activations) are here with the reference's signatures and file names, drawn with matplotlib
-from numbers taken on the device (gradient_stats, activation_stats: ampnet_amd/stats.py) instead of from host copies of
-the tensors; seaborn's KDE curve and torch.mode are not reproduced.  Out of scope: the PCA featuriser variant (:185-237).
-The per-node Python
-sampling loop of :132-149 is replaced by csrc/featurizer.hip; the random stream is this library's (seeded);
-`forward(data, feature_indices=...)` takes the indices of another stream (tests: the reference's own).
-Pinned against the reference's class by tests/golden/model_*.npz (oracle/make_golden_ampgcn.py).
+What is mirrored.  Reference src/ampnet/module/amp_gcn.py:20-118 gives the constructor arguments and the sub-module
+names, and therefore the state-dict keys: feature_embedding_table, conv1, conv2, final_linear_out.  Its forward
+(:239-276) is
+    dropout_adj -> featurise -> drop1 -> conv1 -> ReLU -> drop2 -> conv2 -> ReLU -> drop3 -> token pooling
+    -> Linear -> log_softmax
+with both poolings of :268-271 (token mean, or token 0 with `average_pooling_flag=False`) and both featuriser branches of
+:120-183 (feature_tokens.py).  The model is pinned against the reference's class by tests/golden/model_*.npz
+(oracle/make_golden_ampgcn.py).  Out of scope: the PCA featuriser variant (:185-237).
+
+One walk, three sites.  `_run` is the only function that knows the layer sequence:
+    tokens -> entry -> conv1 -> between -> conv2 -> readout -> pooled [N, embedding_dim]
+The constructor picks the three site objects once.  Plain: the PyTorch ops (_TorchSite around drop1 / drop2 / drop3,
+torch's random stream).  `fused_glue=True`: one fused HIP pass per site (ampnet_amd/glue.py), masks from this library's
+seeded stream.  `layer_norm=True`: the per-token LayerNorm sites norm1, norm2 of
+experiments/cora_overfit_one_subgraph.py:46-107 (ampnet_amd/norm.py) in place of `between` and `readout`.  Every site
+is called as `site(x)` in the forward pass; `site.activate(x)` is the same site with dropout off and without the pooling,
+which is what the activation diagnostics show.
+
+Behind the walk.  `forward` applies final_linear_out and the log_softmax / sigmoid, as one HIP kernel with
+`fused_head=True`; `nll_loss` fuses the training loss and its metrics behind the head as well (ampnet_amd/head.py).  The
+gradient and activation diagnostics of :278-405 are in diagnostics.py.
+
+The random streams.  The per-node Python sampling loop of :132-149 is replaced by csrc/featurizer.hip with this
+library's own seeded stream; `forward(data, feature_indices=...)` takes the indices of another stream (the tests use the
+reference's own).
 
 `storage_dtype=torch.bfloat16` (not in the reference): the two AMPConv layers, their parameters and every [N, L*D] tensor
 between the featuriser and the pooling are stored in bf16 -- the library's fastest edge and projection kernels --; the
@@ -28,135 +37,32 @@ import torch.nn.functional as F
 
 from .. import _lib
 from ..conv import AMPConv
-from ..glue import ActDropout, TokenReadout, act_dropout
+from ..glue import ActDropout, TokenReadout
 from ..head import MAX_CLASSES, classifier_head, saint_nll_loss
-from ..norm import NormTokenReadout, TokenLayerNorm, norm_act_dropout
-from ..stats import tensor_stats
-from ..graph import _stream
+from ..norm import NormTokenReadout, TokenLayerNorm
+from .diagnostics import Diagnostics
+from .feature_tokens import FeatureTokens
 
 
+class _TorchSite:
+    """A site of the unfused model as PyTorch ops: [ReLU ->] nn.Dropout [-> token pooling], the interface of the fused
+    sites (ampnet_amd/glue.py).  Holds no parameters; `drop` is the model's own drop1 / drop2 / drop3."""
+
+    def __init__(self, drop, relu=True, embed_dim=None, mean=True):
+        self.drop, self.relu, self.embed_dim, self.mean = drop, relu, embed_dim, mean
+
+    def activate(self, x):
+        return F.relu(x) if self.relu else x
+
+    def __call__(self, x):
+        x = self.drop(self.activate(x))
+        if self.embed_dim is None:
+            return x
+        x = x.reshape(x.shape[0], x.shape[1] // self.embed_dim, self.embed_dim)
+        return x.mean(dim=1) if self.mean else x[:, 0]                        # token mean / token 0 (amp_gcn.py:268-271)
 
 
-class _BuildTokens(torch.autograd.Function):
-    """tokens[n, l] = concat(table[idx[n, l]], zscore(x)[n, idx[n, l]]); gradient to `table` only
-    (x is data; the reference's x_.requires_grad_(True) leaf is never used by an optimiser).  `dtype` is the storage of
-    the tokens (float32 or bfloat16: the fp32 value rounded to nearest even) and of the gradient that comes back for them;
-    the table and its gradient are fp32 either way."""
-
-    @staticmethod
-    def forward(ctx, table, x, mean, inv_std, idx, dtype=torch.float32):
-        lib = _lib.load()
-        if table.dtype != torch.float32:
-            raise ValueError(f'the feature embedding table is {table.dtype}: it stays float32 (the featuriser kernels read '
-                             f'fp32; AMPGCN(storage_dtype=torch.bfloat16) casts the conv layers only)')
-        N, Fdim = x.shape
-        L, De = idx.size(1), table.size(1)
-        out = torch.empty(N, L, De + 1, dtype=dtype, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.ampconv_feat_build_as(x.data_ptr(), mean.data_ptr(), inv_std.data_ptr(), idx.data_ptr(),
-                                                 table.data_ptr(), N, Fdim, L, De, out.data_ptr(), _lib.DTYPES[dtype],
-                                                 _stream()), 'ampconv_feat_build_as')
-        ctx.save_for_backward(idx)
-        ctx.dims = (N, L, De, table.size(0))
-        ctx.storage = dtype
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        lib = _lib.load()
-        (idx,) = ctx.saved_tensors
-        N, L, De, Fdim = ctx.dims
-        dtable = torch.empty(Fdim, De, dtype=torch.float32, device=dout.device)
-        dout = dout.to(ctx.storage).contiguous()
-        with torch.cuda.device(dout.device):
-            _lib.check(lib.ampconv_feat_table_grad_from(dout.data_ptr(), idx.data_ptr(), N, L, De, Fdim, dtable.data_ptr(),
-                                                        _lib.DTYPES[ctx.storage], _stream()), 'ampconv_feat_table_grad_from')
-        return dtable, None, None, None, None, None
-
-
-class FeatureTokens(nn.Module):
-    """z-score + present-feature sampling + embedding concat (amp_gcn.py:120-183, downsampling branch)."""
-
-    def __init__(self, num_node_features, feat_emb_dim, num_sampled_vectors, seed=0, token_dtype=torch.float32):
-        super().__init__()
-        if token_dtype not in _lib.DTYPES:
-            raise ValueError(f'tokens are written as float32 or bfloat16, not {token_dtype}')
-        self.token_dtype = token_dtype
-        self.feature_embedding_table = nn.Embedding(num_embeddings=num_node_features, embedding_dim=feat_emb_dim)
-        self.num_sampled_vectors = num_sampled_vectors
-        self._seed, self._calls = int(seed), 0
-
-    def zscore_stats(self, x):
-        lib = _lib.load()
-        N, Fdim = x.shape
-        mean = torch.empty(Fdim, dtype=torch.float32, device=x.device)
-        inv_std = torch.empty(Fdim, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.ampconv_feat_zscore_stats(x.data_ptr(), N, Fdim, mean.data_ptr(), inv_std.data_ptr(),
-                                                     _stream()), 'ampconv_feat_zscore_stats')
-        return mean, inv_std
-
-    def sample(self, x, seed=None):
-        lib = _lib.load()
-        N, Fdim = x.shape
-        L = self.num_sampled_vectors
-        idx = torch.empty(N, L, dtype=torch.int32, device=x.device)
-        empty = torch.zeros(1, dtype=torch.int32, device=x.device)
-        if seed is None:
-            self._calls += 1
-            seed = (self._seed * 1000003 + self._calls) & (2 ** 64 - 1)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.ampconv_feat_sample_present(x.data_ptr(), N, Fdim, L, seed, idx.data_ptr(),
-                                                       empty.data_ptr(), _stream()), 'ampconv_feat_sample_present')
-        return idx, empty
-
-    def forward_all(self, x, feature_repeats):
-        """Full-width branch (amp_gcn.py:170-181): token f of a node = concat(tile(table, feature_repeats)[f],
-        zscore(x)[node, f]) for EVERY feature column f; no sampling (returns indices None like the reference)."""
-        if not x.is_cuda or x.dtype != torch.float32:
-            raise ValueError('FeatureTokens needs float32 node features on the GPU (no CPU fallback)')
-        x = x.contiguous()
-        reps = int(feature_repeats) if feature_repeats else 1
-        table = self.feature_embedding_table.weight
-        if reps > 1:
-            table = table.repeat(reps, 1)                       # torch.tile(weight, [feature_repeats, 1])
-        if table.size(0) != x.size(1) or x.size(1) != self.num_sampled_vectors:
-            raise ValueError(f'full-width tokens need num_node_features * feature_repeats ({table.size(0)}) == '
-                             f'x.shape[1] ({x.size(1)}) == num_sampled_vectors ({self.num_sampled_vectors}) '
-                             '(torch.cat / reshape of amp_gcn.py:174-181 raise otherwise)')
-        idx = torch.arange(x.size(1), dtype=torch.int32, device=x.device).repeat(x.size(0), 1)
-        mean, inv_std = self.zscore_stats(x)
-        tokens = _BuildTokens.apply(table.contiguous(), x, mean, inv_std, idx, self.token_dtype)
-        return tokens.view(x.size(0), -1), None
-
-    def forward(self, x, idx=None):
-        if not x.is_cuda or x.dtype != torch.float32:
-            raise ValueError('FeatureTokens needs float32 node features on the GPU (no CPU fallback)')
-        x = x.contiguous()
-        if idx is not None:
-            idx = torch.as_tensor(idx, device=x.device)
-            # given indices go straight into table[f] and x[n, f] on the device: refuse what would read out of bounds
-            # (one read-back, on this replay path only)
-            if idx.dim() != 2 or idx.size(0) != x.size(0) or idx.numel() == 0 or idx.is_floating_point():
-                raise ValueError(f'feature indices must be integers [{x.size(0)}, num_sampled_vectors], got '
-                                 f'{idx.dtype} {tuple(idx.shape)}')
-            lo, hi = int(idx.min()), int(idx.max())
-            width = min(x.size(1), self.feature_embedding_table.num_embeddings)
-            if lo < 0 or hi >= width:
-                raise ValueError(f'feature indices outside [0, {width}): min {lo}, max {hi}')
-            idx = idx.to(torch.int32)
-        if idx is None:
-            idx, empty = self.sample(x)
-            if int(empty.item()):
-                raise ValueError('a node has no present (non-zero) feature to sample from '
-                                 '(np.random.choice raises in the reference, amp_gcn.py:135)')
-        mean, inv_std = self.zscore_stats(x)
-        tokens = _BuildTokens.apply(self.feature_embedding_table.weight, x, mean, inv_std, idx.contiguous(),
-                                    self.token_dtype)
-        return tokens.view(x.size(0), -1), idx
-
-
-class AMPGCN(nn.Module):
+class AMPGCN(Diagnostics, nn.Module):
     def __init__(self, device="cuda", embedding_dim=100, num_heads=2, num_node_features=1433,
                  num_sampled_vectors=40, output_dim=7, softmax_out=True, feat_emb_dim=99, val_emb_dim=1,
                  downsample_feature_vectors=True, average_pooling_flag=True, dropout_rate=0.1,
@@ -224,6 +130,12 @@ class AMPGCN(nn.Module):
         self.fused_head = bool(fused_head)
         if self.fused_head and output_dim > MAX_CLASSES:
             raise ValueError(f'fused_head supports output_dim <= {MAX_CLASSES}, got {output_dim}')
+        # the three sites of _run's walk (entry, between, readout), picked once; a tuple, so nothing is registered twice
+        torch_sites = (_TorchSite(self.drop1, relu=False), _TorchSite(self.drop2),
+                       _TorchSite(self.drop3, embed_dim=embedding_dim, mean=average_pooling_flag))
+        self._sites = tuple(self._glue) if self.fused_glue else torch_sites
+        if self.layer_norm:
+            self._sites = (self._sites[0], self.norm1, self.norm2)
 
     def _check_storage(self):
         """model.float() / model.to(torch.bfloat16) cast every parameter; the kernels behind the table, the norm sites and
@@ -236,10 +148,10 @@ class AMPGCN(nn.Module):
                              f'a cast of the whole model (model.float(), model.to(torch.bfloat16)) is not a storage mode -- '
                              f'construct the model with the storage_dtype you want')
 
-    def _pooled(self, data, feature_indices=None):
-        """forward() up to the token pooling: [N, embedding_dim], the input of final_linear_out.
-        (_activation_sites below walks the same layer sequence in eval mode and keeps every intermediate tensor: a change
-        of the sequence here has to be made there as well; tests/test_gpu_diagnostics.py holds the two together.)"""
+    def _run(self, data, feature_indices=None, sites=None):
+        """The layer walk up to the token pooling: [N, embedding_dim], the input of final_linear_out.  Sets
+        conv1_embedding, conv2_embedding and sampled_node_feat_indices.  sites: a dict that receives, in this order, the
+        tensors the diagnostics show -- both layer outputs, each followed by its site's activate(), and the pooled rows."""
         self._check_storage()
         x, edge_index = data.x.to(self.device), data.edge_index.to(self.device)
         if self.training and self.dropout_adj_rate > 0:                       # dropout_adj (amp_gcn.py:241)
@@ -250,23 +162,22 @@ class AMPGCN(nn.Module):
         else:
             x, sampled = self._tokens[0].forward_all(x, self.feature_repeats)
         self.sampled_node_feat_indices = sampled
-        for site in self._glue:
-            site.train(self.training)
-        x = self.conv1(self._glue[0](x) if self.fused_glue else self.drop1(x), edge_index)
-        self.conv1_embedding = x
-        if self.layer_norm:                                                   # norm -> ReLU -> dropout (-> pooling): one pass each
-            x = self.conv2(self.norm1(x), edge_index)
-            self.conv2_embedding = x
-            return self.norm2(x)
-        if self.fused_glue:
-            x = self.conv2(self._glue[1](x), edge_index)
-            self.conv2_embedding = x
-            return self._glue[2](x)
-        x = self.conv2(self.drop2(F.relu(x)), edge_index)
-        self.conv2_embedding = x
-        x = self.drop3(F.relu(x))
-        x = x.reshape(x.shape[0], x.shape[1] // self.emb_dim, self.emb_dim)
-        return x.mean(dim=1) if self.average_pooling_flag else x[:, 0]      # token mean / token 0 (amp_gcn.py:268-271)
+        for site in self._glue:                                               # a plain list, not sub-modules: train() and
+            site.train(self.training)                                         # eval() miss them
+        entry, between, readout = self._sites
+        self.conv1_embedding = h1 = self.conv1(entry(x), edge_index)
+        self.conv2_embedding = h2 = self.conv2(between(h1), edge_index)
+        pooled = readout(h2)
+        if sites is not None:
+            act = 'LayerNorm+ReLU' if self.layer_norm else 'ReLU'
+            shown = {'AmpConv 1': h1, act + ' 1': between.activate(h1), 'AmpConv 2': h2, act + ' 2': readout.activate(h2),
+                     'Average Pooling' if self.average_pooling_flag else 'Class Token': pooled}
+            sites.update((k, v.contiguous()) for k, v in shown.items())
+        return pooled
+
+    def _pooled(self, data, feature_indices=None):
+        """forward() up to the token pooling: [N, embedding_dim], the input of final_linear_out."""
+        return self._run(data, feature_indices)
 
     def nll_loss(self, data, y=None, node_norm=None, masks=None, grad_mask=0, metrics=None, feature_indices=None):
         """The reference's training loss (F.nll_loss(model(data), y, reduction='none') * node_norm)[masks[grad_mask]].sum()
@@ -305,188 +216,3 @@ class AMPGCN(nn.Module):
             num_features = self.num_node_features
         return getattr(self, layer).attention_heatmap(self.sampled_node_feat_indices, src_features, dst_features,
                                                       num_features=num_features, **selection)
-
-    # ---- diagnostics (amp_gcn.py:278-405): the numbers on the device, the figures from the numbers
-    def gradient_stats(self, bins=30, median=True):
-        """A TensorStats (ampnet_amd.tensor_stats) over the gradients the reference plots (amp_gcn.py:283,325): the
-        parameters with "weight" in their name and a gradient, by name, in named_parameters() order -- counts, min / max /
-        absmax, mean / absmean / std, a `bins`-bin histogram over each gradient's own range and the median.  Launches on
-        the current stream and returns at once; `.read()` is the one synchronisation.  No `mode` (:297): on continuous
-        data torch.mode returns the minimum, `zeros` and `min` say what it would."""
-        grads = {n: p.grad for n, p in self.named_parameters() if 'weight' in n and p.grad is not None}
-        return tensor_stats({n: g if g.is_contiguous() else g.contiguous() for n, g in grads.items()}, bins=bins,
-                            median=median)
-
-    def _diagnostic_seed(self):
-        return (self._tokens[0]._seed * 1000003 + 0x5D1A6) & (2 ** 64 - 1)     # no call counter in it
-
-    def activation_stats(self, data, bins=50, feature_indices=None):
-        """A TensorStats over the activations of an eval-mode, no_grad forward pass of `data` (amp_gcn.py:345-390), by
-        site: "AmpConv 1", "ReLU 1", "AmpConv 2", "ReLU 2", "Average Pooling" (or "Class Token"), "Linear Out" (the logits
-        before the log-softmax / sigmoid); with layer_norm=True the activations are "LayerNorm+ReLU 1" / "LayerNorm+ReLU 2"
-        (the fused site never writes the bare norm).  Per site: counts (zeros / numel of a ReLU site is its dead share),
-        moments, a `bins`-bin histogram over the site's own range and the median.  Where the configured forward fuses the
-        second activation into the pooling (fused_glue, layer_norm) that site is materialised for this call only, by the
-        same kernel family without the pooling.
-
-        Differences from the reference: it stores both ReLUs under the key "ReLU 1", so its first one is lost -- both are
-        kept here; it leaves the model in eval mode -- the previous `training` flag of every sub-module is restored
-        here.  As forward does,
-        the call sets conv1_embedding, conv2_embedding and sampled_node_feat_indices.  It advances NO seeded stream of the
-        library: dropout is off, and the feature indices are `feature_indices`, else this model's
-        sampled_node_feat_indices if they fit data.x (the batch that was just trained on), else drawn with a fixed seed
-        that leaves the sampler's call counter alone (no check for nodes without present features: that would be a
-        read-back)."""
-        flags = [(m, m.training) for m in list(self.modules()) + list(self._glue)]
-        self.eval()
-        try:
-            with torch.no_grad():
-                sites = self._activation_sites(data, feature_indices)
-        finally:
-            for m, flag in flags:                                      # every module's own flag, not the root's for all
-                m.training = flag
-        return tensor_stats(sites, bins=bins, median=True)
-
-    def _activation_sites(self, data, feature_indices):
-        self._check_storage()
-        x, edge_index = data.x.to(self.device), data.edge_index.to(self.device)
-        if self.downsampling_vectors:
-            idx = feature_indices
-            if idx is None and self.sampled_node_feat_indices is not None \
-                    and self.sampled_node_feat_indices.shape[0] == x.shape[0]:
-                idx = self.sampled_node_feat_indices
-            if idx is None:
-                idx = self._tokens[0].sample(x.contiguous(), seed=self._diagnostic_seed())[0]
-            x, sampled = self._tokens[0](x, idx)
-        else:
-            x, sampled = self._tokens[0].forward_all(x, self.feature_repeats)
-        self.sampled_node_feat_indices = sampled
-        for site in self._glue:                                        # a plain list, not sub-modules: eval() misses them
-            site.train(False)
-        D, sites = self.emb_dim, {}
-
-        def activation(h, norm):
-            if self.layer_norm:
-                return norm_act_dropout(h, D, norm.weight, norm.bias, norm.eps, 0.0, norm.activation, False)
-            return act_dropout(h, 0.0, 'relu', False) if self.fused_glue else F.relu(h)
-
-        act_name = 'LayerNorm+ReLU' if self.layer_norm else 'ReLU'
-        h = self.conv1(x, edge_index)                                  # drop1 is the identity in eval mode
-        self.conv1_embedding = sites['AmpConv 1'] = h
-        a = sites[act_name + ' 1'] = activation(h, getattr(self, 'norm1', None))
-        h = self.conv2(a, edge_index)
-        self.conv2_embedding = sites['AmpConv 2'] = h
-        a = sites[act_name + ' 2'] = activation(h, getattr(self, 'norm2', None))
-        if self.layer_norm:
-            pooled = self.norm2(h)
-        elif self.fused_glue:
-            pooled = self._glue[2](h)
-        else:
-            a = a.reshape(a.shape[0], a.shape[1] // D, D)
-            pooled = a.mean(dim=1) if self.average_pooling_flag else a[:, 0]
-        sites['Average Pooling' if self.average_pooling_flag else 'Class Token'] = pooled.contiguous()
-        sites['Linear Out'] = F.linear(pooled.float(), self.final_linear_out.weight, self.final_linear_out.bias)
-        return {k: v.contiguous() for k, v in sites.items()}
-
-    @staticmethod
-    def _figure(*args, **kwargs):
-        """matplotlib's object interface on the Agg canvas: no pyplot state, no global backend switch."""
-        try:
-            from matplotlib.backends.backend_agg import FigureCanvasAgg
-            from matplotlib.figure import Figure
-        except ImportError as e:
-            raise ImportError('the figures need matplotlib, which is not installed; the numbers behind them do not: '
-                              'AMPGCN.gradient_stats() / AMPGCN.activation_stats(data) return them') from e
-        fig = Figure(*args, **kwargs)
-        FigureCanvasAgg(fig)
-        return fig
-
-    @staticmethod
-    def _bars(ax, s, color, density=False):
-        h, edges = s['hist'].astype('float64'), s['edges']
-        width = edges[1:] - edges[:-1]
-        if density and h.sum() > 0 and (width > 0).all():
-            h = h / (h.sum() * width)
-        if not (width > 0).all():                                      # a constant tensor: one bar of unit width
-            edges, width = edges[:-1] - 0.5, 1.0
-        else:
-            edges = edges[:-1]
-        ax.bar(edges, h, width=width, align='edge', color=color, alpha=0.6)
-
-    def plot_grad_flow(self, save_path, epoch_idx, iter, stats=None):
-        """amp_gcn.py:308-343: max- and mean-|gradient| bars per weight, written to
-        <save_path>/gradient_flow_plots/gradient_flow_ep{epoch_idx}_itr{iter}; one read-back.  Returns the dict of
-        gradient_stats(bins=0, median=False).read() it drew from.  stats: a gradient_stats() result queued earlier (or its
-        read() dict) to draw instead of the gradients as they are now."""
-        import os
-        stats = self._read(stats) if stats is not None else self.gradient_stats(bins=0, median=False).read()
-        fig = self._figure()
-        ax = fig.add_subplot()
-        layers = list(stats)
-        at = list(range(len(layers)))
-        ax.bar(at, [stats[n]['absmax'] for n in layers], alpha=0.1, lw=1, color='c')
-        ax.bar(at, [stats[n]['absmean'] for n in layers], alpha=0.1, lw=1, color='b')
-        ax.hlines(0, 0, len(layers) + 1, lw=2, color='k')
-        ax.set_xticks(at)
-        ax.set_xticklabels(layers, rotation='vertical')
-        ax.set_xlim(left=0, right=max(len(layers), 1))
-        ax.set_ylim(bottom=-0.001, top=0.02)                           # the reference's zoom on the low-gradient region
-        ax.set_xlabel('Layers')
-        ax.set_ylabel('average gradient')
-        ax.set_title('Gradient flow')
-        ax.grid(True)
-        from matplotlib.lines import Line2D
-        ax.legend([Line2D([0], [0], color=c, lw=4) for c in 'cbk'], ['max-gradient', 'mean-gradient', 'zero-gradient'])
-        out = os.path.join(save_path, 'gradient_flow_plots')
-        os.makedirs(out, exist_ok=True)
-        fig.savefig(os.path.join(out, f'gradient_flow_ep{epoch_idx}_itr{iter}'), bbox_inches='tight', facecolor='white')
-        return stats
-
-    @staticmethod
-    def _read(stats):
-        return stats.read() if hasattr(stats, 'read') else stats
-
-    def visualize_gradients(self, save_path, epoch_idx, iter, color="C0", stats=None):
-        """amp_gcn.py:278-306: a 30-bin histogram per weight gradient with mean, median, std and the share of zeros in
-        its title (no KDE curve, no mode), written to <save_path>/gradient_distrib_plots/
-        gradient_distrib_epoch{epoch_idx}_itr{iter}; one read-back.  Returns the dict of gradient_stats().read().
-        stats: as for plot_grad_flow (it needs bins and the median)."""
-        import os
-        stats = self._read(stats) if stats is not None else self.gradient_stats(bins=30, median=True).read()
-        columns = max(len(stats), 1)
-        fig = self._figure(figsize=(columns * 4, 4))
-        for i, (name, s) in enumerate(stats.items()):
-            ax = fig.add_subplot(1, columns, i + 1)
-            self._bars(ax, s, color)
-            ax.set_title(f'{name}\nMean: {s["mean"]:.4f}, Median: {s["median"]:.4f}\nSTD: {s["std"]:.4f}, '
-                         f'zeros: {s["zeros"] / max(s["numel"], 1):.1%}')
-            ax.set_xlabel('Grad magnitude')
-        fig.suptitle('Gradient Magnitude Distribution', fontsize=14, y=1.05)
-        fig.subplots_adjust(wspace=0.45)
-        out = os.path.join(save_path, 'gradient_distrib_plots')
-        os.makedirs(out, exist_ok=True)
-        fig.savefig(os.path.join(out, f'gradient_distrib_epoch{epoch_idx}_itr{iter}'), bbox_inches='tight',
-                    facecolor='white')
-        return stats
-
-    def visualize_activations(self, save_path, data, epoch_idx, iter, color="C0", stats=None):
-        """amp_gcn.py:345-406: a 50-bin density histogram per activation site of activation_stats(data), written to
-        <save_path>/act_distrib_ep{epoch_idx}_iter{iter}; one read-back.  Unlike the reference the model's training
-        flag is restored and both ReLU sites are shown.  Returns the dict of activation_stats(data).read().  stats: an
-        activation_stats() result queued earlier (or its read() dict); `data` is then not looked at."""
-        import math
-        import os
-        stats = self._read(stats) if stats is not None else self.activation_stats(data, bins=50).read()
-        columns = 2
-        rows = math.ceil(len(stats) / columns)
-        fig = self._figure(figsize=(columns * 2.7, rows * 2.5))
-        for i, (name, s) in enumerate(stats.items()):
-            ax = fig.add_subplot(rows, columns, i + 1)
-            self._bars(ax, s, color, density=True)
-            ax.set_title(f'{name}\nmean {s["mean"]:.3g}, median {s["median"]:.3g}\nstd {s["std"]:.3g}, '
-                         f'zeros {s["zeros"] / max(s["numel"], 1):.1%}', fontsize=8)
-        fig.suptitle('Activation distribution', fontsize=16)
-        fig.subplots_adjust(hspace=0.9, wspace=0.4)
-        os.makedirs(save_path, exist_ok=True)
-        fig.savefig(os.path.join(save_path, f'act_distrib_ep{epoch_idx}_iter{iter}'))
-        return stats

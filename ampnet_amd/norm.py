@@ -182,6 +182,10 @@ class TokenLayerNorm(_SeededSite):
         return norm_act_dropout(x, self.embed_dim, self.weight, self.bias, self.eps, self.p, self.activation, self.training,
                                 self._next_seed())
 
+    def activate(self, x):
+        """The site with dropout off (and, in NormTokenReadout, without the pooling); advances no counter."""
+        return norm_act_dropout(x, self.embed_dim, self.weight, self.bias, self.eps, 0.0, self.activation, False)
+
     def extra_repr(self):
         return (f'embed_dim={self.embed_dim}, eps={self.eps}, elementwise_affine={self.elementwise_affine}, p={self.p}, '
                 f'activation={self.activation!r}')

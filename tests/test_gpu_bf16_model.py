@@ -111,7 +111,7 @@ def test_bf16_tokens_are_the_rounded_fp32_tokens(width):
 def test_table_gradient_from_a_bf16_token_gradient(shape):
     """The float-atomic accumulation of tests/test_gpu_featurizer.py on a widened bf16 gradient, at that file's bar
     (rtol = atol = 1e-5): N L / F = 12 and 36 unit-size terms per table element."""
-    from ampnet_amd.module.amp_gcn import FeatureTokens
+    from ampnet_amd.module.feature_tokens import FeatureTokens
     L, D, _ = SHAPES[shape]
     torch.manual_seed(41)
     ft = FeatureTokens(FEATS, D - 1, L, token_dtype=BF16).to(DEV)
@@ -137,7 +137,7 @@ def test_full_width_tokens_in_bf16():
     """The full-width branch (every feature column a token, the table tiled feature_repeats times): bf16 tokens are the
     rounded fp32 ones, the gradient of the untiled table stays fp32 and is the fp32 branch's (384 unit-size terms per
     element, float atomics in both: the bar of test_table_gradient_from_a_bf16_token_gradient)."""
-    from ampnet_amd.module.amp_gcn import FeatureTokens
+    from ampnet_amd.module.feature_tokens import FeatureTokens
     torch.manual_seed(43)
     ft32 = FeatureTokens(16, 7, FEATS).to(DEV)
     ft16 = FeatureTokens(16, 7, FEATS, token_dtype=BF16).to(DEV)
@@ -155,7 +155,7 @@ def test_full_width_tokens_in_bf16():
 
 
 def test_a_bf16_embedding_table_is_refused():
-    from ampnet_amd.module.amp_gcn import FeatureTokens
+    from ampnet_amd.module.feature_tokens import FeatureTokens
     ft = FeatureTokens(FEATS, 7, 8).to(DEV).to(BF16)
     with pytest.raises(ValueError, match='stays float32'):
         ft(_graph()[0].to(DEV), _indices(8).to(DEV))
@@ -167,7 +167,7 @@ def _composition(model, data, idx):
     """What AMPGCN(storage_dtype=bfloat16) computes in eval mode, from public pieces that take no storage_dtype: fp32
     tokens cast to bf16, a bf16 AMPConv per layer with the model's parameters, the glue / norm sites, the head."""
     from ampnet_amd import AMPConv, act_dropout, act_dropout_pool, classifier_head, norm_act_dropout, norm_act_dropout_pool
-    from ampnet_amd.module.amp_gcn import FeatureTokens
+    from ampnet_amd.module.feature_tokens import FeatureTokens
     L, D, H = model.num_sampled_vectors, model.emb_dim, model.conv1.num_heads
     ft = FeatureTokens(FEATS, D - 1, L)
     ft.feature_embedding_table = model.feature_embedding_table

@@ -184,6 +184,50 @@ def test_activation_stats_advances_no_stream(dev, name):
             assert torch.equal(grads_a[n], grads_b[n]), n
 
 
+@pytest.mark.parametrize('name,fixture', [(n, 'model_cora.npz') for n in CONFIGS]
+                         + [('plain', 'model_xor_tok0.npz'), ('fused_glue', 'model_xor_tok0.npz')])
+def test_sites_are_the_forward_pass(dev, name, fixture):
+    """What the diagnostics record is the forward pass itself: in eval mode _run with a `sites` dict returns _pooled's
+    tensor bit for bit, a site's activate() is the site (dropout is off) without its pooling, and nothing is advanced.
+    The token mean against a float64 mean of activate(): (L - 1) additions of the ascending fp32 sum, each rounding a
+    partial sum <= k max, then one reciprocal and one product -- ((L + 1) / 2 + 2) 2^-24 max_l |a[n, l, c]| per element."""
+    model, data = _build(dev, CONFIGS[name], fixture)
+    D, mean = model.emb_dim, model.average_pooling_flag
+    idx = model._tokens[0].sample(data.x, seed=17)[0] if model.downsampling_vectors else None    # a seed given: no counter
+    seeded = list(model._glue) + ([model.norm1, model.norm2] if model.layer_norm else [])
+    assert len(seeded) == {'fused_glue': 3, 'layer_norm': 2}.get(name, 0)
+    counters = lambda: ([(s._calls, s.last_seed) for s in seeded], model._tokens[0]._calls)
+    before = counters()
+    model.eval()
+    with torch.no_grad():
+        pooled = model._pooled(data, idx)
+        sites = {}
+        out = model._run(data, idx, sites)
+        assert torch.equal(out, pooled) and pooled.shape == (data.x.shape[0], D) and float(pooled.abs().sum()) > 0
+        assert list(sites) == _sites(CONFIGS[name], 'Average Pooling' if mean else 'Class Token')[:-1]
+        h1, h2 = sites['AmpConv 1'], sites['AmpConv 2']
+        assert torch.equal(h1, model.conv1_embedding) and torch.equal(h2, model.conv2_embedding)
+        _, between, readout = model._sites
+        a1, a2 = between.activate(h1), readout.activate(h2)
+        assert torch.equal(between(h1), a1) and a1.shape == h1.shape and a2.shape == h2.shape
+        act = 'LayerNorm+ReLU' if model.layer_norm else 'ReLU'
+        assert torch.equal(sites[act + ' 1'], a1) and torch.equal(sites[act + ' 2'], a2)
+        got = readout(h2)
+        assert torch.equal(got, pooled)
+        if mean:
+            L = a2.shape[1] // D
+            a = a2.view(-1, L, D).double()
+            bound = ((L + 1) / 2 + 2) * 2.0 ** -24 * a.abs().amax(dim=1)
+            err = (got.double() - a.mean(dim=1)).abs()
+            live = bound > 0
+            print(f'[tol] {name} token mean, L = {L}: largest share of the bound '
+                  f'{float((err[live] / bound[live]).max()):.3f}, dead channels {int((~live).sum())}')
+            assert bool((err <= bound).all()), (name, float((err - bound).max()))
+        else:
+            assert torch.equal(got, a2[:, :D])
+    assert counters() == before
+
+
 def test_reference_named_figures(dev, tmp_path):
     """The harness's calls (experiments/cora_benchmark_graphsaint.py:111-114), argument for argument."""
     pytest.importorskip('matplotlib')
