@@ -69,6 +69,7 @@ class AMPConv(MessagePassing):
         # raises instead of pinning tens of GB after backward.
         self.retain_attention = 'auto'
         self._attn_dropped_bytes = 0
+        self._attn_token_only = False         # the last call was forward_token (fast path): no per-edge side outputs
         self._attn_param_versions = None
         # how the per-node projections run: 'native' (default: libampconv's own kernels, csrc/proj_gemm.hip -- fp32
         # operands as two fp16 planes of the power-of-two-scaled value, three partial products on the matrix cores
@@ -137,6 +138,33 @@ class AMPConv(MessagePassing):
         self._set_attn_ctx(qkv, None, edge_index, L, shared=True, plane_bounds=bounds)
         return y
 
+    def forward_token(self, x, edge_index, token=0):
+        """`self.forward(x, edge_index).view(N, L, D)[:, token]`, values and gradients (to x and the four parameters),
+        [N, embed_dim]: the layer for a model that reads ONE token of its output (AMPGCN(average_pooling_flag=False)
+        reads token 0 of conv2, amp_gcn.py:266-271).  The query rows are x.view(N, L, D)[:, token]; the Q projection, the
+        out-projection and their gradients run over N rows instead of N * L, the edge passes are the one-query-token
+        family (csrc/edge_token.hip; functional.AMPConvTokenFunction).  Where that family does not serve the shape
+        (ampconv_token_supported), for softmax=False layers and under AMPCONV_FORCE_GENERIC=1 this IS the full layer and
+        a slice.  The per-edge side outputs (attn_output, attn_output_weights, attention_heatmap) are not available
+        after this call: they raise."""
+        self._check_x(x)
+        D = self.embed_dim
+        N, L = x.size(0), x.size(1) // D
+        token = int(token)
+        if not 0 <= token < L:
+            raise ValueError(f'token must be in [0, {L}), got {token}')
+        if (not self.softmax or os.environ.get('AMPCONV_FORCE_GENERIC', '0')[:1] == '1'
+                or not F_.token_supported(L, D, self.num_heads, x.dtype)):
+            return self.forward(x, edge_index).view(N, L, D)[:, token]
+        if edge_index.device != x.device:
+            raise ValueError(f'edge_index is on {edge_index.device} but x is on {x.device}')
+        csr = graph_cache.get(edge_index, N)
+        self._attn_ctx = self._attn_output = self._attn_output_weights = None
+        self._attn_dropped_bytes = 0
+        self._attn_token_only = True
+        return F_.AMPConvTokenFunction.apply(x.reshape(N, L, D)[:, token], x, *self._params(), csr, self.num_heads,
+                                             self.gemm_precision)
+
     def message(self, x_i, x_j):
         """Pass messages from nodes x_j to nodes x_i: per-edge cross-attention of the
         pre-gathered pairs, [E, L*D] (amp_conv.py:28-51)."""
@@ -176,6 +204,7 @@ class AMPConv(MessagePassing):
         self._attn_output_weights = None
         self._attn_ctx = None
         self._attn_dropped_bytes = 0
+        self._attn_token_only = False
         nbytes = q_buf.numel() * q_buf.element_size() + (0 if kv_buf is None else kv_buf.numel() * kv_buf.element_size())
         keep = self.retain_attention
         if keep == 'auto':
@@ -192,6 +221,9 @@ class AMPConv(MessagePassing):
         self._attn_param_versions = (m.out_proj.weight._version, m.out_proj.bias._version)
 
     def _attn_missing(self, name):
+        if getattr(self, '_attn_token_only', False):
+            raise RuntimeError(f'{name} is not available after forward_token: that call projects ONE query row per node '
+                               f'and keeps no [N*L, 3D] projection buffer; run forward() for the per-edge outputs')
         if self._attn_dropped_bytes:
             raise RuntimeError(
                 f'{name} was not retained: the projection buffer of the last forward is '

@@ -461,6 +461,106 @@ class AMPConvFunction(torch.autograd.Function):
         return dxq, dxkv, dw_in, db_in, dw_out, db_out, None, None, None, None, None
 
 
+def token_supported(L, D, H, dtype):
+    """Do the one-query-token edge kernels (csrc/edge_token.hip) serve this shape at this storage dtype?"""
+    return dtype in _lib.DTYPES and bool(_lib.load().ampconv_token_supported(L, D, H, _lib.DTYPES[dtype]))
+
+
+def _token_view(buf2d, dh):
+    """ampconv_view_t of a contiguous one-token tensor [N, D]: element (n, h, c) at n * D + h * dh + c."""
+    assert buf2d.is_contiguous() and buf2d.dtype in (torch.float32, torch.bfloat16)
+    return _lib.View(buf2d.data_ptr(), buf2d.size(1), buf2d.size(1), dh)
+
+
+class AMPConvTokenFunction(torch.autograd.Function):
+    """AMPConvFunction for ONE query token per node: y [N, D] = mask(deg>0) * (mean_in-edges(attention of the query row
+    xq_tok[d] over the L tokens of xkv[s]) Wo^T + bo) -- what `AMPConvFunction(x, x, ...)[:, token]` computes when xq_tok is
+    token `token` of x, without the Q projection, the out-projection and their gradients over the other L - 1 query rows,
+    and without the [N, L*D] output.  Differentiable in xq_tok [N, D], xkv [N, L*D] and the four parameters.  The K | V
+    projection and the per-edge gather of the source's K and V tiles are those of the full layer; the edge passes are
+    ampconv_*_edge_token (include/ampconv.h).  Projections in the plain fp32 / bf16 modes (no scaled or plane operands);
+    bf16 storage with 16 <= L <= 128: the N*L-row products run over the nodes with out-edges only (node lists)."""
+
+    @staticmethod
+    def forward(ctx, xq_tok, xkv, w_in, b_in, w_out, b_out, csr, num_heads, gemm='fp32'):
+        D = w_out.size(0)
+        H = int(num_heads)
+        dh = D // H
+        N, L = xkv.size(0), xkv.size(1) // D
+        if w_in.dtype != xkv.dtype or w_out.dtype != xkv.dtype or xq_tok.dtype != xkv.dtype:
+            raise ValueError(f'inputs are {xq_tok.dtype} / {xkv.dtype} but the parameters are {w_in.dtype}: storage is all '
+                             f'float32 or all bfloat16 (layer.to(torch.bfloat16))')
+        if xq_tok.shape != (N, D):
+            raise ValueError(f'xq_tok must be [{N}, {D}], got {tuple(xq_tok.shape)}')
+        if not token_supported(L, D, H, xkv.dtype):
+            raise ValueError(f'the one-query-token kernels do not serve L = {L}, head dimension {dh}, {xkv.dtype} '
+                             f'(ampconv_token_supported): use the full layer and a slice')
+        code = _lib.DTYPES[xkv.dtype]
+        lib = _lib.load()
+        with torch.cuda.device(xkv.device), gemm_precision(gemm):
+            xkv2 = xkv.contiguous().view(N * L, D)
+            native = proj_native(gemm, xkv.dtype, D)
+            out_nodes = None
+            if NODE_LISTS and native and xkv.dtype == torch.bfloat16 and 16 <= L <= 128 and N == csr.num_nodes:
+                lists = csr.active_nodes()
+                out_nodes = lists and lists['out']
+            proj = Projections(native, [w_in[:D], w_in[D:], w_out])
+            q = proj.forward(0, xq_tok, b_in[:D])                                          # [N, D]
+            # (node lists: K / V rows matter for nodes with out-edges; the others are never read and stay unwritten)
+            kv = proj.forward(1, xkv2, b_in[D:], nodes=out_nodes, L=L)                     # [N*L, 2D]
+            obar = torch.empty(N, D, dtype=xkv.dtype, device=xkv.device)
+            hub, nch, ws = csr.hub_args('dst', 1, D, 1)
+            _lib.check(lib.ampconv_fwd_edge_token(_token_view(q, dh), _view(kv, 0, L, dh), _view(kv, D, L, dh),
+                                                  csr.rowptr.data_ptr(), csr.col.data_ptr(), N, L, D, H,
+                                                  _token_view(obar, dh), hub, nch, _ptr(ws), code, _stream()),
+                       'ampconv_fwd_edge_token')
+            # bias and the in-degree mask: rows nobody sends to stay exactly 0
+            y = proj.forward(-1, obar, b_out, mask=(csr.rowptr, N), L=1)
+        ctx.save_for_backward(xq_tok, xkv2, w_in, w_out, q, kv, obar)
+        ctx.csr, ctx.dims, ctx.proj, ctx.gemm, ctx.out_nodes, ctx.code = csr, (N, L, D, H), proj, gemm, out_nodes, code
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xq_tok, xkv2, w_in, w_out, q, kv, obar = ctx.saved_tensors
+        csr, (N, L, D, H), proj, out_nodes, code = ctx.csr, ctx.dims, ctx.proj, ctx.out_nodes, ctx.code
+        dh = D // H
+        dev = dy.device
+        lib = _lib.load()
+        with torch.cuda.device(dev), gemm_precision(ctx.gemm):
+            dy2 = dy.contiguous()
+            # out-projection: rows with no in-edge contribute nothing (their obar is 0, the bias gradient masks them)
+            dw_out = torch.empty_like(w_out)
+            db_out = torch.empty(D, dtype=dy2.dtype, device=dev)
+            proj.weight_grad([(dy2, obar, None)], dw_out, db_out, mask=(csr.rowptr, N), L=1)
+            dobar = proj.input_grad(-1, dy2)                                               # [N, D]
+            dq = torch.empty(N, D, dtype=dy2.dtype, device=dev)
+            dkv = torch.empty(N * L, 2 * D, dtype=dy2.dtype, device=dev)
+            Qv, Kv, Vv, dOv = _token_view(q, dh), _view(kv, 0, L, dh), _view(kv, D, L, dh), _token_view(dobar, dh)
+            hub, nch, ws = csr.hub_args('dst', 1, D, 1)
+            _lib.check(lib.ampconv_bwd_edge_dst_token(Qv, Kv, Vv, dOv, csr.rowptr.data_ptr(), csr.col.data_ptr(), N, L, D, H,
+                                                      _token_view(dq, dh), hub, nch, _ptr(ws), code, _stream()),
+                       'ampconv_bwd_edge_dst_token')
+            hub, nch, ws = csr.hub_args('src', L, D, 2)
+            _lib.check(lib.ampconv_bwd_edge_src_token(Qv, Kv, Vv, dOv, csr.cscptr.data_ptr(), csr.crow.data_ptr(),
+                                                      csr.cinv.data_ptr(), N, L, D, H, _view(dkv, 0, L, dh),
+                                                      _view(dkv, D, L, dh), hub, nch, _ptr(ws), code, _stream()),
+                       'ampconv_bwd_edge_src_token')
+            del dobar, ws
+            # in-projection: the Q third from the N-row term, the K | V thirds from the N*L-row term; all three thirds of
+            # db_in are the true column sums (rows without edges are exact zeros, both passes wrote them)
+            dw_in = torch.empty_like(w_in)
+            db_in = torch.empty(3 * D, dtype=dy2.dtype, device=dev)
+            proj.weight_grad([(dq, xq_tok, None)], dw_in[:D], db_in[:D])
+            proj.weight_grad([(dkv, xkv2, None)], dw_in[D:], db_in[D:], nodes=out_nodes, L=L)
+            dxq = dxkv = None
+            if ctx.needs_input_grad[0]:
+                dxq = proj.input_grad(0, dq)
+            if ctx.needs_input_grad[1]:
+                dxkv = proj.input_grad(1, dkv, mask=out_nodes and (out_nodes[2], N), nodes=out_nodes, L=L).view(N, L * D)
+        return dxq, dxkv, dw_in, db_in, dw_out, db_out, None, None, None
+
+
 def attention_weights(Qv, Kv, edge_index, L, D, H):
     """[E, L, L] head-averaged softmax weights in ORIGINAL edge order
     (amp_conv.py:39,43-47; torch functional.py:6604-6606)."""

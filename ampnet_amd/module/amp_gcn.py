@@ -30,6 +30,16 @@ reference's own).
 between the featuriser and the pooling are stored in bf16 -- the library's fastest edge and projection kernels --; the
 embedding table, the LayerNorm sites and final_linear_out stay fp32, and so does every accumulation.  Train it with
 ampnet_amd.FusedAdam, which steps the bf16 parameters on fp32 masters.
+
+`readout_token_only=True` (not in the reference; needs `average_pooling_flag=False`): conv2 is computed for the read-out
+token only, `conv2.forward_token(between(h1), edge_index, 0)` -- its Q projection, out-projection and their gradients run
+over N rows instead of N*L, its edge passes are the one-query-token family (csrc/edge_token.hip) -- and the readout site
+receives [N, D]: one token, pooling `token0` over L = 1.  In eval mode, or with dropout_rate=0, outputs and gradients
+equal the unflagged model's within the fp32 (bf16) bars of the tests.  In training, drop3's mask on [N, D] is another
+draw from the same distribution than the unflagged model's mask on [N, L*D] -- for torch's stream and for the seeded
+fused stream alike, which is keyed by element index.  conv2_embedding and the 'AmpConv 2' / activation diagnostics are
+[N, D]; attention_heatmap(layer='conv2') raises; conv1 is untouched.  nll_loss, fused_head, fused_glue, layer_norm and
+storage_dtype=torch.bfloat16 all work with the flag.
 """
 import torch
 import torch.nn as nn
@@ -67,8 +77,12 @@ class AMPGCN(Diagnostics, nn.Module):
                  num_sampled_vectors=40, output_dim=7, softmax_out=True, feat_emb_dim=99, val_emb_dim=1,
                  downsample_feature_vectors=True, average_pooling_flag=True, dropout_rate=0.1,
                  dropout_adj_rate=0.1, feature_repeats=5, seed=0, fused_glue=False, fused_head=False, layer_norm=False,
-                 storage_dtype=torch.float32):
+                 storage_dtype=torch.float32, readout_token_only=False):
         super().__init__()
+        if readout_token_only and average_pooling_flag:
+            raise ValueError('readout_token_only=True needs average_pooling_flag=False: with the token mean every token '
+                             'of conv2 is read')
+        self.readout_token_only = bool(readout_token_only)
         if storage_dtype not in _lib.DTYPES:
             raise ValueError(f'storage_dtype is torch.float32 or torch.bfloat16, got {storage_dtype}')
         self.storage_dtype = storage_dtype
@@ -166,7 +180,10 @@ class AMPGCN(Diagnostics, nn.Module):
             site.train(self.training)                                         # eval() miss them
         entry, between, readout = self._sites
         self.conv1_embedding = h1 = self.conv1(entry(x), edge_index)
-        self.conv2_embedding = h2 = self.conv2(between(h1), edge_index)
+        if self.readout_token_only:                                           # [N, D]: token 0 is all the readout reads
+            self.conv2_embedding = h2 = self.conv2.forward_token(between(h1), edge_index, 0)
+        else:
+            self.conv2_embedding = h2 = self.conv2(between(h1), edge_index)
         pooled = readout(h2)
         if sites is not None:
             act = 'LayerNorm+ReLU' if self.layer_norm else 'ReLU'

@@ -4,7 +4,7 @@ MI355X path, on a synthetic Cora-shaped graph (Cora itself is a network download
 AMPGCN(D=128, H=4, L=20) + GraphSAINT random-walk batches + Adam + cosine warm restarts +
 node_norm-weighted NLL.  Everything between the data and the loss runs on the GPU.
 
-    python examples/train_graphsaint.py [--epochs 3] [--dropout 0.1 --fused-glue] [--fused-head] [--layer-norm]
+    python examples/train_graphsaint.py [--epochs 3] [--dropout 0.1 --fused-glue] [--fused-head] [--layer-norm] [--token-readout]
                                         [--fused-adam [--clip M] [--track-grad-norm] [--bf16]] [--diagnostics K [--diag-dir DIR]]
                                         [--model gcn [--gcn-input {embedded,zscore,raw}] [--hidden 16]]
 
@@ -103,6 +103,9 @@ def main(argv=None):
     ap.add_argument('--bf16', action='store_true',
                     help='AMPGCN(storage_dtype=torch.bfloat16): the two AMPConv layers and the activations between them in '
                          'bf16 storage, table / norms / head in fp32; needs --fused-adam, which keeps fp32 master weights')
+    ap.add_argument('--token-readout', action='store_true',
+                    help='read token 0 of conv2 instead of the token mean (average_pooling_flag=False) and compute conv2 for '
+                         'that token only: AMPGCN(readout_token_only=True), AMPConv.forward_token')
     ap.add_argument('--diagnostics', type=int, default=0, metavar='K',
                     help="every K-th batch queues the reference's gradient and activation diagnostics (experiments/"
                          'cora_benchmark_graphsaint.py:111-114) as device-side statistics (AMPGCN.gradient_stats / '
@@ -120,8 +123,8 @@ def main(argv=None):
                  'master copies and writes the rounded result')
     if args.bf16 and args.model == 'gcn':
         ap.error('--bf16 belongs to --model ampgcn (GCN is float32 only)')
-    if args.model == 'gcn' and (args.layer_norm or args.diagnostics > 0 or args.class_defaults):
-        ap.error('--layer-norm, --diagnostics and --class-defaults belong to --model ampgcn')
+    if args.model == 'gcn' and (args.layer_norm or args.diagnostics > 0 or args.class_defaults or args.token_readout):
+        ap.error('--layer-norm, --diagnostics, --class-defaults and --token-readout belong to --model ampgcn')
     device = torch.device('cuda:0')
     torch.manual_seed(1)
     data = synthetic_cora(device)
@@ -135,9 +138,11 @@ def main(argv=None):
         model = AMPGCN(device=device, embedding_dim=D, num_heads=H, num_node_features=1433, num_sampled_vectors=L,
                        output_dim=7, softmax_out=True, feat_emb_dim=D - 1, val_emb_dim=1, dropout_rate=args.dropout,
                        dropout_adj_rate=0.0, fused_glue=args.fused_glue, fused_head=args.fused_head,
-                       layer_norm=args.layer_norm,
+                       layer_norm=args.layer_norm, average_pooling_flag=not args.token_readout,
+                       readout_token_only=args.token_readout,
                        storage_dtype=torch.bfloat16 if args.bf16 else torch.float32).to(device)
-        what = 'sampler + 2 AMPConv layers fwd+bwd + Adam' + (', bf16 storage' if args.bf16 else '')
+        what = 'sampler + 2 AMPConv layers fwd+bwd + Adam' + (', bf16 storage' if args.bf16 else '') + (
+            ', conv2 for the read-out token only' if args.token_readout else '')
     loader = GraphSAINTRandomWalkSampler(data, batch_size=8, walk_length=150, num_steps=args.steps,
                                          sample_coverage=20, seed=1)
     if args.fused_adam:

@@ -306,6 +306,44 @@ int ampconv_bwd_edge_src_scaled(ampconv_view_t Q, ampconv_view_t K, ampconv_view
                                 int64_t hub_chunks, void *hub_ws, const float *bounds,
                                 const float *stats, float *out_absmax, void *stream);
 
+/* ---- edge phase, ONE query token per node (csrc/edge_token.hip) ------------------------------------------------------
+ * The three passes for a layer whose output is read at a single token per node (AMPGCN(average_pooling_flag=False)
+ * reads token 0 of conv2, src/ampnet/module/amp_gcn.py:266-271).  The arithmetic is that of "edge phase, forward /
+ * backward" above with ONE query row per (node, head):
+ *   Q, dObar, O, dQ   views whose element (n, h, c) is at ptr + n*node_stride + h*head_stride + c; row_stride is
+ *                     ignored.  Token t of an [N, L, D] tensor is selected by offsetting ptr by t*row_stride elements.
+ *   K, V, dK, dV      L tokens per node, as in every other family.
+ * Per destination row d, head h and in-edge s -> d, deg = in-degree of d:
+ *   p = softmax_j(q_h . K[s,j,h] / sqrt(dh))   (length L)
+ *   O[d,h] = (1/deg) sum_edges sum_j p_j V[s,j,h]                     (exactly 0 when deg = 0)
+ * backward, g = dObar[d,h] / deg (dObar is the gradient of the MEAN; `cinv` as in ampconv_bwd_edge_src):
+ *   dp_j = g . V[s,j,h];  ds = p (dp - sum p dp)
+ *   dQ[d,h] = sum_edges sum_j ds_j K[s,j,h] / sqrt(dh)               (exactly 0 when deg = 0)
+ *   dK[s,j,h] = sum_out-edges ds_j q_h / sqrt(dh);  dV[s,j,h] = sum_out-edges p_j g    (exactly 0 without out-edges)
+ * No atomics: every output row has one owner, sums run in CSR / CSC order, results are bitwise reproducible.  No
+ * softmax statistics: the source pass keeps K[s], V[s] of its own node on chip and recomputes the softmax and
+ * sum p dp per out-edge from the destination's q and dObar rows.  Long segments: the plans of ampconv_hub_plan; the
+ * workspace holds [1, D] partial tiles for the forward and destination pass (ampconv_hub_workspace_bytes(n, 1, D, 1))
+ * and [L, D] x 2 for the source pass (ampconv_hub_workspace_bytes(n, L, D, 2)), combined in the fixed order of every
+ * other family.  Rows from n_rows / n_src on are not touched.  dtype: AMPCONV_F32 or AMPCONV_BF16 (bf16 in HBM, fp32
+ * softmax and accumulation, one rounding on the way out).  K / V rows are read in 16-byte pieces where bases, strides
+ * and dh allow, else in 8-, 4- (or, bf16, 2-) byte pieces: no view is refused for its alignment.
+ * ampconv_token_supported: 1 for L <= 64, dh <= 64 (bf16: even dh).  Null pointers, D % H != 0, an unsupported shape or
+ * dtype, or a hub workspace without a plan return AMPCONV_E_BADARG / AMPCONV_E_DTYPE before anything is launched.
+ * These entry points were added without a change of AMPCONV_VERSION (no existing argument list changed).  */
+int ampconv_token_supported(int L, int D, int H, int dtype);
+int ampconv_fwd_edge_token(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, const int32_t *rowptr,
+                           const int32_t *col, int64_t n_rows, int L, int D, int H, ampconv_view_t O,
+                           const void *hub_plan, int64_t hub_chunks, void *hub_ws, int dtype, void *stream);
+int ampconv_bwd_edge_dst_token(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, ampconv_view_t dObar,
+                               const int32_t *rowptr, const int32_t *col, int64_t n_rows, int L, int D, int H,
+                               ampconv_view_t dQ, const void *hub_plan, int64_t hub_chunks, void *hub_ws, int dtype,
+                               void *stream);
+int ampconv_bwd_edge_src_token(ampconv_view_t Q, ampconv_view_t K, ampconv_view_t V, ampconv_view_t dObar,
+                               const int32_t *cscptr, const int32_t *crow, const float *cinv, int64_t n_src, int L,
+                               int D, int H, ampconv_view_t dK, ampconv_view_t dV, const void *hub_plan,
+                               int64_t hub_chunks, void *hub_ws, int dtype, void *stream);
+
 /* ---- per-edge side outputs, ORIGINAL edge order ------------------------------
  * attn_weights: W[e] = mean_h softmax_rows(Q[dst e,:,h] K[src e,:,h]^T/sqrt(dh)),
  * [E, L, L] fp32 -- `self.attn_output_weights` (amp_conv.py:39,43-47; torch
