@@ -20,9 +20,11 @@ from .norm import NormTokenReadout, TokenLayerNorm, norm_act_dropout, norm_act_d
 from .optim import FusedAdam
 from .stats import TensorStats, tensor_stats
 from .gcn import gcn_aggregate, gcn_input_linear, gcn_norm
+from .pair_loss import PairLoss, pair_loss, walk_pairs
 
 __all__ = ['AMPConv', 'InvalidConfiguration', 'EdgeCSR', 'graph_cache', 'distributed', 'AMPGCN', 'FeatureTokens',
            'GraphSAINTRandomWalkSampler', 'NodePartition', 'PartitionedAMPConv', 'GraphedAMPConv', 'AttentionHeatmap', 'top_features',
            'ActDropout', 'TokenReadout', 'act_dropout', 'act_dropout_pool', 'HeadMetrics', 'classifier_head', 'saint_nll_loss',
            'NormTokenReadout', 'TokenLayerNorm', 'norm_act_dropout', 'norm_act_dropout_pool', 'FusedAdam',
-           'TensorStats', 'tensor_stats', 'GCNConv', 'GCN', 'gcn_norm', 'gcn_aggregate', 'gcn_input_linear']
+           'TensorStats', 'tensor_stats', 'GCNConv', 'GCN', 'gcn_norm', 'gcn_aggregate', 'gcn_input_linear',
+           'pair_loss', 'PairLoss', 'walk_pairs']

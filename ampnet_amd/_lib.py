@@ -200,6 +200,11 @@ SIGNATURES = {
     'ampconv_gcn_input_workspace_bytes': (_sz, [_i64, _i64, _i32]),
     'ampconv_gcn_input_fwd': (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _sz, _vp]),
     'ampconv_gcn_input_bwd': (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    'ampconv_pair_loss_workspace_bytes': (_sz, [_i64, _i64, _i32]),
+    'ampconv_pair_loss_fwd': (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i32, ctypes.c_float,
+                                     ctypes.c_float, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
+    'ampconv_pair_loss_bwd': (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i32, ctypes.c_float,
+                                     ctypes.c_float, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _sz, _i32, _vp]),
 }
 
 _lib = None

@@ -196,6 +196,12 @@ class AMPGCN(Diagnostics, nn.Module):
         """forward() up to the token pooling: [N, embedding_dim], the input of final_linear_out."""
         return self._run(data, feature_indices)
 
+    def embed(self, data, feature_indices=None):
+        """The node embeddings: the pooled [N, embedding_dim] rows in front of final_linear_out, with their gradient --
+        what an unsupervised loss trains (ampnet_amd.pair_loss).  Sets conv1_embedding, conv2_embedding and
+        sampled_node_feat_indices as forward does."""
+        return self._pooled(data, feature_indices)
+
     def nll_loss(self, data, y=None, node_norm=None, masks=None, grad_mask=0, metrics=None, feature_indices=None):
         """The reference's training loss (F.nll_loss(model(data), y, reduction='none') * node_norm)[masks[grad_mask]].sum()
         with the head, the loss and the metrics of every mask fused into one kernel per direction and no device

@@ -988,6 +988,60 @@ int ampconv_gcn_input_bwd(const float *x, int64_t N, int64_t F, const float *mea
                           const float *table, int De, int C, const float *g, int64_t ld_g, float *dW, float *dtable,
                           void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- pair loss ----------------------------------------------------------------
+ * The unsupervised GraphSAGE loss the reference announces and leaves empty (synthetic_benchmark/contrastive_ssl_AMPNet.py
+ * and predictive_ssl_AMPNet.py:79, `criterion = None  # Implement GraphSAGE unsupervised loss function`, with the
+ * TensorFlow affinity / neg_cost / _skipgram_loss it means quoted at :14-49), over (anchor, positive, negatives) triples
+ * of node embeddings.  Added without a version change, like the entry points of 111 before it: no existing argument list
+ * changes.
+ *   Z [N, D] fp32 or bf16 (`dtype`), row stride ldz >= D elements, 1 <= D <= AMPCONV_PAIR_MAX_D (odd D included);
+ *   anchor[B], positive[B], negative[S] int64 node ids; weight[B] fp32 or NULL (1; no gradient flows to it);
+ *   scale: a temperature's reciprocal; neg_weight: used by AMPCONV_PAIR_XENT only; exclude_anchor: 0 or 1.
+ * With a_b = Z[anchor[b]], p_b = Z[positive[b]], n_s = Z[negative[s]]:
+ *   aff_b = scale <a_b, p_b>,   g_bs = scale <a_b, n_s>;
+ *   a pair (b, s) is KEPT unless exclude_anchor is set and negative[s] == anchor[b] (compared on the clamped ids);
+ *   AMPCONV_PAIR_SKIPGRAM: l_b = log sum_{kept s} exp(g_bs) - aff_b.  This is the quoted _skipgram_loss NEGATED: as quoted,
+ *       sum(aff - neg_cost) is a quantity to maximise; the library returns what an optimizer minimises.  A row with no
+ *       kept negative has a negative term of 0.
+ *   AMPCONV_PAIR_XENT:     l_b = softplus(-aff_b) + neg_weight sum_{kept s} softplus(g_bs)   (GraphSAGE's _xent_loss);
+ *   loss = sum_b weight_b l_b.  B = 0: loss 0 and zero gradients.
+ * Gradient for the upstream scalar g0 (read from the device, `gout`), with pi_bs = the softmax over the kept s
+ * (skipgram) or neg_weight sigmoid(g_bs) (xent), c_b = -1 (skipgram) or -sigmoid(-aff_b) (xent):
+ *   dZ[anchor[b]]   += g0 w_b scale (sum_s pi_bs n_s + c_b p_b)
+ *   dZ[positive[b]] += g0 w_b scale c_b a_b
+ *   dZ[negative[s]] += g0 scale sum_b w_b pi_bs a_b
+ * A node may hold all three roles and repeat in each list; dZ sums every contribution.
+ * FORWARD writes aff[B], neg_term[B] (the kept log-sum-exp, or the softplus sum), the scalar loss (a device float) and
+ * `oob` (device int32): non-zero if any id lies outside [0, N).  Such ids are clamped on their int64 value before any
+ * address is formed -- v < 0 -> 0, v >= N -> N - 1, as ampconv_csr_build does -- and the result is that of the clamped
+ * ids.  The [B, S] logits are tiled on chip and never written; rows of Z are read through the index arrays (no gathered
+ * copies); the log-sum-exp is online (running maximum and sum), so no exponential overflows at any logit.  Where B alone
+ * does not fill the card the S range is split over workgroups and the partial (max, sum) pairs merge in split order.
+ * BACKWARD recomputes the logits from Z, aff and neg_term in two atomic-free passes -- over anchor tiles (pi N; the
+ * positive role falls out of it) and over negative tiles (pi^T A) -- into dense fp32 role gradients in the workspace
+ * (rows padded to a multiple of 4 floats; the streamed side split as above, one partial per split), then folds them into
+ * dZ [N, D] (row stride lddz, Z's dtype) per node, in the order of the caller's node-sorted slot list: slot b < B is
+ * anchor b, B + b positive b, 2 B + s negative s; slot_idx[2 B + S] holds the slots sorted (stably) by clamped node id and
+ * slot_ptr[N + 1] the segment of every node.  dZ is written in full, +0 for the nodes without a role.  Slots and segment
+ * bounds are clamped, so a malformed list cannot fault.  Loss and dZ are bitwise reproducible: no floating-point atomics.
+ * Products on v_mfma_f32_16x16x4_f32 (exact fp32; bf16 rows widened on load), K zero-padded.
+ * workspace: ampconv_pair_loss_workspace_bytes(B, S, D) bytes (covers either direction), 256-byte aligned, not zeroed.
+ * REFUSED with AMPCONV_E_BADARG, nothing launched or written: D outside [1, AMPCONV_PAIR_MAX_D], ldz < D (lddz < D),
+ * S < 1 or N < 1 with B > 0, a NULL Z or index pointer with B > 0, a NULL output, an unknown kind or dtype, N above
+ * 2^31 - 1, B or S above 2^29; AMPCONV_E_WORKSPACE: a short workspace.  */
+#define AMPCONV_PAIR_MAX_D 256
+enum { AMPCONV_PAIR_SKIPGRAM = 0, AMPCONV_PAIR_XENT = 1 };
+size_t ampconv_pair_loss_workspace_bytes(int64_t B, int64_t S, int D);
+int ampconv_pair_loss_fwd(const void *Z, int64_t N, int D, int64_t ldz, const int64_t *anchor, const int64_t *positive,
+                          int64_t B, const int64_t *negative, int64_t S, const float *weight, int kind, float scale,
+                          float neg_weight, int exclude_anchor, float *aff, float *neg_term, float *loss, int32_t *oob,
+                          void *workspace, size_t workspace_bytes, int dtype, void *stream);
+int ampconv_pair_loss_bwd(const void *Z, int64_t N, int D, int64_t ldz, const int64_t *anchor, const int64_t *positive,
+                          int64_t B, const int64_t *negative, int64_t S, const float *weight, int kind, float scale,
+                          float neg_weight, int exclude_anchor, const float *aff, const float *neg_term,
+                          const float *gout, const int32_t *slot_ptr, const int32_t *slot_idx, void *dZ, int64_t lddz,
+                          void *workspace, size_t workspace_bytes, int dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
