@@ -205,6 +205,8 @@ SIGNATURES = {
                                      ctypes.c_float, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
     'ampconv_pair_loss_bwd': (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i32, ctypes.c_float,
                                      ctypes.c_float, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _sz, _i32, _vp]),
+    'ampconv_knn_workspace_bytes': (_sz, [_i64, _i64, _i64, _i32, _i32]),
+    'ampconv_knn': (_i32, [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
 }
 
 _lib = None

@@ -1042,6 +1042,61 @@ int ampconv_pair_loss_bwd(const void *Z, int64_t N, int D, int64_t ldz, const in
                           const float *gout, const int32_t *slot_ptr, const int32_t *slot_idx, void *dZ, int64_t lddz,
                           void *workspace, size_t workspace_bytes, int dtype, void *stream);
 
+/* ---- nearest neighbours -------------------------------------------------------
+ * The k best keys of every query among the rows of one node matrix: what a trained embedding is used for (nearest-
+ * neighbour evaluation, ampnet_amd.knn_classify) and what the reference's synthetic benchmark builds its graphs with
+ * (synthetic_benchmark/synthetic_xor.py:69-101, scikit-learn's NearestNeighbors, ampnet_amd.knn_graph).  Added without
+ * a version change, like the pair loss: no existing argument list changes.
+ *   X [N, D] fp32 or bf16 (`dtype`), row stride ldx >= D elements, 1 <= D <= AMPCONV_KNN_MAX_D (odd D included);
+ *   query[Q], key[S] int64 node ids, or NULL: the list is every node in order (its count must then be N; a count of 0
+ *   is taken with either); 1 <= k <= AMPCONV_KNN_MAX_K; N, Q, S <= 2^31 - 1; exclude_self: 0 or 1.
+ * Ids outside [0, N) are clamped on their int64 value before any address is formed -- v < 0 -> 0, v >= N -> N - 1, as
+ * ampconv_pair_loss_fwd and ampconv_csr_build do --, set *oob (device int32) non-zero, and the result is that of the
+ * clamped ids; *oob is 0 otherwise.
+ * GOODNESS g of the pair (q, s), with a = X[query[q]], b = X[key[s]], products and sums in fp32 (bf16 rows widened on
+ * load), <a, b> on v_mfma_f32_16x16x4_f32 (exact fp32), K zero-padded:
+ *   AMPCONV_KNN_DOT:    g = <a, b>;
+ *   AMPCONV_KNN_COSINE: g = (<a, b> r_a) r_b,  r = 1 / max(sqrt(sum of squares), 1e-12)  (torch.nn.functional.normalize's
+ *                       epsilon);
+ *   AMPCONV_KNN_L2:     d2 = max(fma(-2, <a, b>, |a|^2 + |b|^2), 0),  g = -d2.  This is the EXPANSION, not a sum of squared
+ *                       differences: its absolute error is of the order of 2^-24 (|a|^2 + |b|^2) however close the two
+ *                       rows are.
+ *   r and |x|^2 are one fp32 value per node, summed in one fixed order per row by a pre-pass into the workspace.
+ * `score` holds g for DOT and COSINE, descending along a row, and d2 for L2, ascending.
+ * SELECTION.  The pair (q, s) is a CANDIDATE unless exclude_self is set and the clamped key id equals the clamped query
+ * id, or its g is NaN (for L2: the value before the max is NaN).  Candidates are totally ordered by (g descending,
+ * s ascending); s is the POSITION in the key list, not the node id; -0 counts as +0; +-infinity are ordinary values.
+ * Row q of the output is the first min(k, #candidates) of its candidates in that order: idx [Q, k] (row stride k) holds
+ * their node ids (the clamped key[s], or s), score [Q, k] their scores.  The slots behind them hold idx = -1 and score =
+ * -infinity (DOT, COSINE) or +infinity (L2).
+ * The order is one unsigned compare of a 64-bit key: high word = the image of g's bits u (0x80000000 first replaced by 0)
+ * under u -> ~u if the sign bit is set, else u | 0x80000000; low word = ~s.  Key 0 is no candidate (-infinity maps to
+ * 0x007FFFFF).
+ * DETERMINISM.  The order is strict and a pair's g does not depend on where the pair falls in a tile, so the result does
+ * not depend on tile order, on how the key range is split over workgroups, on Q, or on the other queries of the call:
+ * two calls give bitwise-equal idx and score, and row q of a call over a query subset equals bitwise that node's row of
+ * the all-rows call.  No atomics.
+ * The [Q, S] scores are tiled on chip and never written; the best k of a row are kept in LDS.  Where Q alone does not
+ * fill the card the key range is split over workgroups, each split writes its k keys per row to the workspace and a
+ * merge takes the best k of a row's partials.
+ * workspace: ampconv_knn_workspace_bytes(Q, S, N, D, k) bytes (non-decreasing in every argument), 256-byte aligned, not
+ * zeroed.
+ * REFUSED with AMPCONV_E_BADARG, nothing launched or written: D outside [1, AMPCONV_KNN_MAX_D], k outside
+ * [1, AMPCONV_KNN_MAX_K], ldx < D, a NULL X, idx, score or oob or N < 1 with Q > 0, a NULL id list whose count is
+ * neither N nor 0, an unknown metric or dtype, a negative N, Q or S or one above 2^31 - 1; AMPCONV_E_WORKSPACE: a
+ * NULL or short workspace.  Q == 0 succeeds and writes only *oob = 0 (if oob is given); S == 0 fills Q rows of empty
+ * slots.  */
+#define AMPCONV_KNN_MAX_D 256
+#define AMPCONV_KNN_MAX_K 64
+enum { AMPCONV_KNN_DOT = 0, AMPCONV_KNN_COSINE = 1, AMPCONV_KNN_L2 = 2 };
+size_t ampconv_knn_workspace_bytes(int64_t Q, int64_t S, int64_t N, int D, int k);
+int ampconv_knn(const void *X, int64_t N, int D, int64_t ldx,
+                const int64_t *query, int64_t Q,      /* node ids, or NULL: Q == N, query q is node q */
+                const int64_t *key, int64_t S,        /* node ids, or NULL: S == N, key s is node s   */
+                int k, int metric, int exclude_self,
+                int64_t *idx, float *score,           /* [Q, k] each, row stride k */
+                int32_t *oob, void *workspace, size_t workspace_bytes, int dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
