@@ -76,6 +76,7 @@ STATS_CHUNK = 4096        # AMPCONV_STATS_CHUNK: elements one workgroup handles 
 STATS_MAX_BINS = 2048     # AMPCONV_STATS_MAX_BINS
 STATS_MAX_RANKS = 4       # AMPCONV_STATS_MAX_RANKS: order statistics per call
 STATS_RECORD_BYTES = 88   # sizeof(ampconv_stats_record_t)
+PCA_RUN, PCA_MAX_W, PCA_MAX_K = 32, 2048, 128    # AMPCONV_PCA_RUN (rows summed in fp32 before the fp64 fold), _MAX_W, _MAX_K
 GCN_LONG_SEGMENT = 256    # AMPCONV_GCN_LONG_SEGMENT: a CSR/CSC segment from this length on is summed by whole workgroups
 
 # name -> (restype, argtypes); mirrors include/ampconv.h one to one
@@ -207,6 +208,12 @@ SIGNATURES = {
                                      ctypes.c_float, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _sz, _i32, _vp]),
     'ampconv_knn_workspace_bytes': (_sz, [_i64, _i64, _i64, _i32, _i32]),
     'ampconv_knn': (_i32, [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
+    'ampconv_pca_shift_workspace_bytes': (_sz, [_i64, _i32, _i32]),
+    'ampconv_pca_shift': (_i32, [_vp, _i64, _i32, _i64, _i32, _vp, _vp, _sz, _i32, _vp]),
+    'ampconv_pca_gram_splits': (_i32, [_i64, _i32]),
+    'ampconv_pca_gram_workspace_bytes': (_sz, [_i64, _i32]),
+    'ampconv_pca_gram': (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
+    'ampconv_pca_project': (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _vp]),
 }
 
 _lib = None

@@ -162,6 +162,11 @@ class AMPGCN(Diagnostics, nn.Module):
                              f'a cast of the whole model (model.float(), model.to(torch.bfloat16)) is not a storage mode -- '
                              f'construct the model with the storage_dtype you want')
 
+    def init_feature_table_from_pca(self, x, freeze=True):
+        """feature_embedding_table.weight = the PCA scores of the feature columns of x [N, num_node_features], the
+        reference's PCA featuriser (FeatureTokens.load_pca_table); freeze=True takes the table out of training."""
+        return self._tokens[0].load_pca_table(x, freeze)
+
     def _run(self, data, feature_indices=None, sites=None):
         """The layer walk up to the token pooling: [N, embedding_dim], the input of final_linear_out.  Sets
         conv1_embedding, conv2_embedding and sampled_node_feat_indices.  sites: a dict that receives, in this order, the

@@ -62,6 +62,24 @@ class FeatureTokens(nn.Module):
     def zscore_stats(self, x):
         return zscore_stats(x)
 
+    def load_pca_table(self, x, freeze=True):
+        """The reference's PCA featuriser (amp_gcn.py:185-206): row f of the table becomes the first feat_emb_dim principal
+        component scores of feature column f of x [N, F] -- `pca.fit_transform(x.numpy().transpose())`, amp_gcn.py:196,
+        under the exact solver (ampnet_amd.pca, samples='columns').  With forward / forward_all this gives its tokens
+        concat(pca_row[f], zscore(x)[n, f]).  freeze: the table takes no gradient from then on (the reference's PCA
+        rows are constants).  Returns the PCAResult."""
+        from ..pca import pca
+        table = self.feature_embedding_table
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.size(1) != table.num_embeddings:
+            raise ValueError(f'load_pca_table: x has to be [N, {table.num_embeddings}] (one column per row of the table), got '
+                             f'{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}')
+        res = pca(x.detach().to(table.weight.device), table.embedding_dim, samples='columns')
+        with torch.no_grad():
+            table.weight.copy_(res.scores)
+        if freeze:
+            table.weight.requires_grad_(False)
+        return res
+
     def sample(self, x, seed=None):
         lib = _lib.load()
         N, Fdim = x.shape

@@ -112,7 +112,12 @@ def main(argv=None):
                          "activation_stats); they are read and printed with the epoch's one read-back")
     ap.add_argument('--diag-dir', default=None, metavar='DIR',
                     help="with --diagnostics: write the reference's three figures for the last queued batch of every epoch there")
+    ap.add_argument('--pca-table', action='store_true',
+                    help="the reference's PCA featuriser (amp_gcn.py:185-206): the feature table is the PCA scores of the feature "
+                         'columns of data.x (AMPGCN.init_feature_table_from_pca, ampnet_amd.pca), frozen')
     args = ap.parse_args(argv)
+    if args.pca_table and args.model == 'gcn':
+        ap.error('--pca-table belongs to --model ampgcn')
     if args.diag_dir is not None and args.diagnostics <= 0:
         ap.error('--diag-dir needs --diagnostics K')
     if (args.clip is not None or args.track_grad_norm) and not args.fused_adam:
@@ -143,14 +148,19 @@ def main(argv=None):
                        storage_dtype=torch.bfloat16 if args.bf16 else torch.float32).to(device)
         what = 'sampler + 2 AMPConv layers fwd+bwd + Adam' + (', bf16 storage' if args.bf16 else '') + (
             ', conv2 for the read-out token only' if args.token_readout else '')
+        if args.pca_table:
+            fit = model.init_feature_table_from_pca(data.x, freeze=True)
+            print(f'feature table = PCA scores of the {data.x.size(1)} feature columns: {D - 1} components hold '
+                  f'{float(fit.explained_variance_ratio.sum()):.1%} of the variance; the table is frozen')
     loader = GraphSAINTRandomWalkSampler(data, batch_size=8, walk_length=150, num_steps=args.steps,
                                          sample_coverage=20, seed=1)
+    trained = [p for p in model.parameters() if p.requires_grad]            # (--pca-table freezes the feature table)
     if args.fused_adam:
-        opt = FusedAdam(model.parameters(), lr=0.005, weight_decay=1e-4, max_grad_norm=args.clip,
+        opt = FusedAdam(trained, lr=0.005, weight_decay=1e-4, max_grad_norm=args.clip,
                         track_grad_norm=args.track_grad_norm)
         zero_grad, step = (lambda: None), (lambda: opt.step(set_to_none=True))
     else:
-        opt = torch.optim.Adam(model.parameters(), lr=0.005, weight_decay=1e-4)
+        opt = torch.optim.Adam(trained, lr=0.005, weight_decay=1e-4)
         zero_grad, step = opt.zero_grad, opt.step
     sched = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(opt, T_0=400, T_mult=2)
     t0 = time.time()

@@ -1097,6 +1097,66 @@ int ampconv_knn(const void *X, int64_t N, int D, int64_t ldx,
                 int64_t *idx, float *score,           /* [Q, k] each, row stride k */
                 int32_t *oob, void *workspace, size_t workspace_bytes, int dtype, void *stream);
 
+/* ---- principal components -------------------------------------------------------
+ * The kernels under ampnet_amd.pca (csrc/pca.hip): the reference's sklearn.decomposition.PCA -- the PCA featuriser
+ * (src/ampnet/module/amp_gcn.py:185-237, fit_transform(x.T)), the explained-variance curve and the 2-D plot
+ * (visualization/plot_PCA_2D_plot.py).  Added without a version change: no existing argument list changes.
+ *
+ * WHAT ampnet_amd.pca COMPUTES is sklearn's PCA(n_components=k, svd_solver='full') of the data X [M, P]:
+ *   samples='rows':    X = x (embeddings [N, D]);   samples='columns': X = x^T, never formed (the reference's
+ *   fit_transform(x.transpose()): the samples are the F feature columns).
+ *   mean [P] = the per-column mean of X over the M samples; Xc = X - mean = U S Vt;
+ *   components = Vt[:k], scores = U[:, :k] S[:k], singular_values = S[:k],
+ *   explained_variance = S^2 / (M - 1), explained_variance_ratio = S^2 / (sum of all S^2), 0 where that sum is 0.
+ *   Sign: every component is flipped so that its largest-magnitude entry is positive, the first such entry on a tie
+ *   (scikit-learn >= 1.5, svd_flip(u_based_decision=False)); the scores flip with it.
+ *   Domain: x [R, W] fp32 or bf16, W <= AMPCONV_PCA_MAX_W, row stride ldx >= W; 2 <= M; 1 <= k <= min(M, P,
+ *   AMPCONV_PCA_MAX_K).
+ *   Rank-deficient directions: where S_j <= S_1 max(M, P) 2^-23, a vector that has to be recovered by a division by
+ *   S_j is written as zeros; S_j itself is reported, clamped at 0.
+ * Whatever `samples` is, the W x W matrix is Sm = A^T A contracted over the stored rows of x:
+ *   'rows':    A[n, w] = x[n, w] - mean[w] (a column shift); Sm is the scatter matrix, its eigenvectors are the
+ *              components and the scores are a projection;
+ *   'columns': A[n, f] = x[n, f] - mean[n] (a row shift); Sm is the Gram matrix of the samples, eigenvectors sqrt(lambda)
+ *              are the scores and the components [k, N] a projection divided by S_j.
+ * The eigen-decomposition of Sm (fp64, W x W) is the caller's.
+ *
+ * Common to the three calls: x [R, W] fp32 or bf16 (`dtype`, bf16 widened on load), 1 <= R <= 2^31 - 1,
+ * 1 <= W <= AMPCONV_PCA_MAX_W, ldx >= W; anything else, a NULL x or output: AMPCONV_E_BADARG, nothing launched.  No
+ * atomics: two calls give bitwise-equal results.
+ *
+ * ampconv_pca_shift: out[w] = the mean of column w over the R rows (axis 0, out [W]) or out[r] = the mean of row r
+ * over the W columns (axis 1, out [R]): summed in fp64 in one fixed order, divided in fp64, written as fp32.  Axis 0
+ * is a two-level reduction: chunks of rows (at most 512, from R alone) into fp64 partial sums in the workspace
+ * (ampconv_pca_shift_workspace_bytes, 0 for axis 1), then the chunks in order.
+ *
+ * ampconv_pca_gram: Sm [W, W] fp64, row stride W, Sm[i][j] = sum over n of A[n, i] A[n, j] with
+ *   A[n, w] = (fp32(x[n, w]) - row_shift[n]) - col_shift[w]  in fp32; a NULL shift is no subtraction, so with one
+ *   shift given the element is rounded once.
+ * Products are exact fp32 on v_mfma_f32_16x16x4_f32, summed in fp32 over a run of at most AMPCONV_PCA_RUN rows; the
+ * runs are added in fp64.  The rows are split over workgroups -- ampconv_pca_gram_splits(R, W) splits, from the shape
+ * alone, their fp64 partials in the workspace (at most 64 MiB from the second split on) -- and a second launch adds
+ * the splits in order.  Only the tiles on and above the diagonal are computed; Sm[j][i] is written from Sm[i][j]: the
+ * result is exactly symmetric.  |Sm - exact| <= (AMPCONV_PCA_RUN + 2) 2^-24 (|A|^T |A|) elementwise.
+ * AMPCONV_E_WORKSPACE: a NULL workspace or one shorter than ampconv_pca_gram_workspace_bytes(R, W).
+ *
+ * ampconv_pca_project: out[r, j] = scale[j] * sum over w of A[r, w] V[w, j], j < k, with A as above; V [W, k] fp32,
+ * row stride k; scale [k] or NULL (1 / S_j, or 0 for a rank-deficient direction); out fp32 [R, k], row stride
+ * ldo >= k; 1 <= k <= AMPCONV_PCA_MAX_K.  The same MFMA, fp32 sums over all of W:
+ * |out - exact| <= (W + 2) 2^-24 |scale| (|A| |V|).  */
+#define AMPCONV_PCA_RUN 32
+#define AMPCONV_PCA_MAX_W 2048
+#define AMPCONV_PCA_MAX_K 128
+size_t ampconv_pca_shift_workspace_bytes(int64_t R, int W, int axis);
+int ampconv_pca_shift(const void *x, int64_t R, int W, int64_t ldx, int axis, float *out, void *workspace,
+                      size_t workspace_bytes, int dtype, void *stream);
+int ampconv_pca_gram_splits(int64_t R, int W);
+size_t ampconv_pca_gram_workspace_bytes(int64_t R, int W);
+int ampconv_pca_gram(const void *x, int64_t R, int W, int64_t ldx, const float *row_shift, const float *col_shift,
+                     double *Sm, void *workspace, size_t workspace_bytes, int dtype, void *stream);
+int ampconv_pca_project(const void *x, int64_t R, int W, int64_t ldx, const float *row_shift, const float *col_shift,
+                        const float *V, int k, const float *scale, float *out, int64_t ldo, int dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
