@@ -23,10 +23,12 @@ from .gcn import gcn_aggregate, gcn_input_linear, gcn_norm
 from .pair_loss import PairLoss, pair_loss, walk_pairs
 from .knn import knn, knn_classify, knn_graph
 from .pca import PCAResult, pca
+from .tsne import TSNEResult, neighbor_preservation, tsne
 
 __all__ = ['AMPConv', 'InvalidConfiguration', 'EdgeCSR', 'graph_cache', 'distributed', 'AMPGCN', 'FeatureTokens',
            'GraphSAINTRandomWalkSampler', 'NodePartition', 'PartitionedAMPConv', 'GraphedAMPConv', 'AttentionHeatmap', 'top_features',
            'ActDropout', 'TokenReadout', 'act_dropout', 'act_dropout_pool', 'HeadMetrics', 'classifier_head', 'saint_nll_loss',
            'NormTokenReadout', 'TokenLayerNorm', 'norm_act_dropout', 'norm_act_dropout_pool', 'FusedAdam',
            'TensorStats', 'tensor_stats', 'GCNConv', 'GCN', 'gcn_norm', 'gcn_aggregate', 'gcn_input_linear',
-           'pair_loss', 'PairLoss', 'walk_pairs', 'knn', 'knn_graph', 'knn_classify', 'pca', 'PCAResult']
+           'pair_loss', 'PairLoss', 'walk_pairs', 'knn', 'knn_graph', 'knn_classify', 'pca', 'PCAResult',
+           'tsne', 'TSNEResult', 'neighbor_preservation']

@@ -1157,6 +1157,86 @@ int ampconv_pca_gram(const void *x, int64_t R, int W, int64_t ldx, const float *
 int ampconv_pca_project(const void *x, int64_t R, int W, int64_t ldx, const float *row_shift, const float *col_shift,
                         const float *V, int k, const float *scale, float *out, int64_t ldo, int dtype, void *stream);
 
+/* ---- t-SNE ------------------------------------------------------------------------
+ * The kernels under ampnet_amd.tsne (csrc/tsne.hip): the reference's visualization/plot_TSNE_2D_plot.py,
+ * TSNE(n_components=2, perplexity=10, learning_rate=10).fit_transform(x.T).  Added without a version change: no
+ * existing argument list changes.
+ *
+ * WHAT ampnet_amd.tsne COMPUTES is scikit-learn 1.7.2's TSNE(method='barnes_hut') with the repulsive term summed
+ * exactly (what its own code computes at angle = 0), for TWO output dimensions only: one degree of freedom,
+ * q_ij = 1 / (1 + |y_i - y_j|^2).
+ *   neighbours: the k = min(M - 1, int(3 perplexity + 1)) nearest other samples by squared Euclidean distance;
+ *   conditional affinities p_{j|i} over those k by the perplexity search below (_utils._binary_search_perplexity);
+ *   P = (p + p^T) / max(sum, 2^-52) as a CSR, indices ascending within a row, a pair that is a neighbour both ways once
+ *   with the summed value, a pair whose fp64 sum is exactly 0 not at all (_t_sne._joint_probabilities_nn, scipy's
+ *   P + P.T); values float32, as _kl_divergence_bh reads them;
+ *   gradient_i = 4 (sum_j P_ij q_ij (y_i - y_j)  -  sum_{j != i} q_ij^2 (y_i - y_j) / max(Z, 2^-52)),
+ *   Z = sum_{i != j} q_ij (_kl_divergence_bh); error = sum_ij P_ij log(max(P_ij, FLT_MIN) / max(q_ij / Z, FLT_MIN));
+ *   the update is _gradient_descent's: gains += 0.2 where update * gradient < 0, else gains *= 0.8, clipped below at
+ *   min_gain = 0.01; gradient *= gains; update = momentum update - learning_rate gradient; y += update; 250 iterations
+ *   at momentum 0.5 on early_exaggeration P, the rest at 0.8 on P with update and gains reset; error and gradient norm
+ *   every 50 iterations and at the last, with scikit-learn's two stopping rules.
+ * Where this differs from scikit-learn: j = i is excluded BY INDEX, so another point that coincides with y_i adds
+ * q = 1 to Z and no force; scikit-learn's tree skips every point at distance 0.  Embeddings without coincident points
+ * (any that has left the 1e-4-scaled start) see no difference.  The start is exact PCA, so nothing is random.
+ *
+ * ampconv_tsne_affinities: dist2 [N, K] fp32 (row stride ldd >= K), 1 <= K <= AMPCONV_TSNE_MAX_K; P [N, K] fp32 (row
+ * stride K) and beta [N] fp64.  Per row, in fp64: beta = 1, the bounds infinite; at most 100 times
+ *   p_j = exp(-dist2_j beta), s = sum p_j (s = 1e-8f if it is 0), p_j /= s, H = log(s) + beta sum dist2_j p_j;
+ *   stop if |H - log(perplexity)| <= 1e-5f; H too large: lower bound = beta, beta doubles while the upper bound is
+ *   infinite, else the midpoint; H too small: upper bound = beta, beta halves while the lower bound is infinite, else
+ *   the midpoint.
+ * P = fp32(p), except that a p that is positive in fp64 and rounds to 0 is written as the smallest fp32 denormal (bits
+ * 0x00000001): whether a pair is an entry of the joint P is decided by p != 0 in fp64, as scipy's P + P.T decides it, and
+ * the consumer reads that off the BITS of P.  beta = the value p was evaluated at.  Every one of the K columns takes part (scikit-learn's K < N
+ * case).  1e-5f, 1e-8f and the perplexity are float32 values widened, as in scikit-learn.  One wave per row; the two
+ * sums are butterflies over the lanes, so they differ from a sequential sum by fp64 rounding only.
+ *
+ * ampconv_tsne_repulsion: y [N, 2] fp32 dense, 8-byte aligned; neg_f [N, 2] fp32, neg_f[i] = sum_{j != i} q_ij^2 (y_i - y_j)
+ * and *Z fp64 (device).  Pair arithmetic is fp32 (y_i - y_j, two FMAs for 1 + d^2, v_rcp_f32: 1 ulp).  For row i the
+ * three sums run over the keys j in ascending order in fp32 for a run of AMPCONV_TSNE_RUN keys (runs start at
+ * multiples of it), the runs of a chunk are added in order in fp64, the chunks in order in fp64, neg_f is rounded
+ * once.  A chunk is AMPCONV_TSNE_CHUNK ceil(ceil(N / AMPCONV_TSNE_CHUNK) / 64) keys: a function of N alone, so is the
+ * launch, and the entry point exposes no split.  Z: the rows' fp64 sums, 256 consecutive rows by a binary tree
+ * (s[t] += s[t + o], o = 128 .. 1), those sums by lane t adding t, t + 256, ... and the same tree.  No atomics: two
+ * calls give the same bits.  |neg_f - exact| <= (AMPCONV_TSNE_RUN + 16) 2^-24 sum_j |q_ij^2 (y_i - y_j)| per
+ * coordinate and |Z_i - exact| <= (AMPCONV_TSNE_RUN + 8) 2^-24 Z_i per row.
+ * Workspace: ampconv_tsne_repulsion_workspace_bytes(N), 8-byte aligned: the chunks' fp64 sums [chunk][3][N], i.e.
+ * 24 bytes x chunks x N with chunks = ceil(N / chunk length) <= 64, plus 8 bytes per 256 rows.  It grows with N^2 up
+ * to 262 144 points and linearly beyond: 55 MB at 96 000 points (24 chunks), 403 MB at 262 144 (64 chunks), 1.5 GB at
+ * a million, 25.8 GB at AMPCONV_TSNE_MAX_N -- the limit of the index arithmetic, not a size the workspace makes cheap.
+ *
+ * ampconv_tsne_step: one iteration.  y_in, y_out (a different buffer: rows read their neighbours' y_in), update, gains,
+ * neg_f [N, 2] fp32 dense and 8-byte aligned, update and gains updated in place; the CSR of P (indptr [N + 1], indices
+ * [nnz] int64, val [nnz] fp32; a column outside [0, N) is clamped, positions outside [0, nnz] likewise); *Z fp64 as
+ * ampconv_tsne_repulsion left it.  Per row i, with p = exaggeration val in fp32 and q as above:
+ *   pos = sum over the row of (p q) (y_i - y_j): lane l of a wave adds the entries l, l + 64, ... in fp32, a butterfly
+ *   adds the lanes; a row longer than AMPCONV_TSNE_PART entries is cut into parts of that length from its start, each
+ *   summed this way, the parts added in order in fp64;
+ *   grad = 4 fp32(pos - neg_f / max(Z, 2^-52)) (the difference in fp64), then the fp32 statements above.
+ * error (NULL: not computed): error[0] = sum of p log(max(p, FLT_MIN) / max(fp32(q / Z), FLT_MIN)) (terms and row sums
+ * in fp32 in the order of pos, rows in fp64), error[1] = sum over the elements of (gains grad)^2 (fp64); both over the
+ * rows by lane t adding t, t + 256, ... and the tree above.
+ * Workspace: ampconv_tsne_step_workspace_bytes(N, nnz), 8-byte aligned.
+ * AMPCONV_E_BADARG (nothing launched): a NULL or misaligned pointer, y_in == y_out, N outside [1, AMPCONV_TSNE_MAX_N],
+ * K outside its range, perplexity <= 0.  AMPCONV_E_WORKSPACE: a NULL or short workspace.  */
+#define AMPCONV_TSNE_MAX_K 256
+#define AMPCONV_TSNE_MAX_N (1 << 24)
+#define AMPCONV_TSNE_RUN 256
+#define AMPCONV_TSNE_TILE 1024
+#define AMPCONV_TSNE_CHUNK 4096
+#define AMPCONV_TSNE_PART 1024
+int ampconv_tsne_affinities(const float *dist2, int64_t N, int K, int64_t ldd, float perplexity, float *P, double *beta,
+                            void *stream);
+size_t ampconv_tsne_repulsion_workspace_bytes(int64_t N);
+int ampconv_tsne_repulsion(const float *y, int64_t N, float *neg_f, double *Z, void *workspace, size_t workspace_bytes,
+                           void *stream);
+size_t ampconv_tsne_step_workspace_bytes(int64_t N, int64_t nnz);
+int ampconv_tsne_step(const float *y_in, float *y_out, float *update, float *gains, int64_t N, const int64_t *indptr,
+                      const int64_t *indices, const float *val, int64_t nnz, const float *neg_f, const double *Z,
+                      float exaggeration, float momentum, float learning_rate, float min_gain, double *error,
+                      void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
