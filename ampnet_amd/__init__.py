@@ -24,6 +24,7 @@ from .pair_loss import PairLoss, pair_loss, walk_pairs
 from .knn import knn, knn_classify, knn_graph
 from .pca import PCAResult, pca
 from .tsne import TSNEResult, neighbor_preservation, tsne
+from .umap import UMAPResult, umap
 
 __all__ = ['AMPConv', 'InvalidConfiguration', 'EdgeCSR', 'graph_cache', 'distributed', 'AMPGCN', 'FeatureTokens',
            'GraphSAINTRandomWalkSampler', 'NodePartition', 'PartitionedAMPConv', 'GraphedAMPConv', 'AttentionHeatmap', 'top_features',
@@ -31,4 +32,4 @@ __all__ = ['AMPConv', 'InvalidConfiguration', 'EdgeCSR', 'graph_cache', 'distrib
            'NormTokenReadout', 'TokenLayerNorm', 'norm_act_dropout', 'norm_act_dropout_pool', 'FusedAdam',
            'TensorStats', 'tensor_stats', 'GCNConv', 'GCN', 'gcn_norm', 'gcn_aggregate', 'gcn_input_linear',
            'pair_loss', 'PairLoss', 'walk_pairs', 'knn', 'knn_graph', 'knn_classify', 'pca', 'PCAResult',
-           'tsne', 'TSNEResult', 'neighbor_preservation']
+           'tsne', 'TSNEResult', 'neighbor_preservation', 'umap', 'UMAPResult']

@@ -167,6 +167,12 @@ class AMPGCN(Diagnostics, nn.Module):
         reference's PCA featuriser (FeatureTokens.load_pca_table); freeze=True takes the table out of training."""
         return self._tokens[0].load_pca_table(x, freeze)
 
+    def init_feature_table_from_umap(self, x, freeze=True, **umap_args):
+        """feature_embedding_table.weight = the UMAP embedding of the feature columns of x [N, num_node_features], the
+        reference's UMAP featuriser (FeatureTokens.load_umap_table); umap_args go to ampnet_amd.umap; freeze=True takes
+        the table out of training."""
+        return self._tokens[0].load_umap_table(x, freeze, **umap_args)
+
     def _run(self, data, feature_indices=None, sites=None):
         """The layer walk up to the token pooling: [N, embedding_dim], the input of final_linear_out.  Sets
         conv1_embedding, conv2_embedding and sampled_node_feat_indices.  sites: a dict that receives, in this order, the

@@ -80,6 +80,26 @@ class FeatureTokens(nn.Module):
             table.weight.requires_grad_(False)
         return res
 
+    def load_umap_table(self, x, freeze=True, **umap_args):
+        """The reference's UMAP featuriser (src/ampnet/utils/preprocess.py:29-68): row f of the table becomes the
+        feat_emb_dim-dimensional UMAP embedding of feature column f of x [N, F] --
+        `UMAP(n_neighbors=15, n_components=feat_emb_dim, min_dist=0.1).fit_transform(x.T)` as ampnet_amd.umap computes it
+        (samples='columns'; umap_args are passed on).  freeze: the table takes no gradient from then on.  Returns the
+        UMAPResult."""
+        from ..umap import umap
+        table = self.feature_embedding_table
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.size(1) != table.num_embeddings:
+            raise ValueError(f'load_umap_table: x has to be [N, {table.num_embeddings}] (one column per row of the table), got '
+                             f'{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}')
+        if 'samples' in umap_args:
+            raise ValueError("load_umap_table: the samples are the feature columns of x (samples='columns')")
+        res = umap(x.detach().to(table.weight.device), table.embedding_dim, samples='columns', **umap_args)
+        with torch.no_grad():
+            table.weight.copy_(res.embedding)
+        if freeze:
+            table.weight.requires_grad_(False)
+        return res
+
     def sample(self, x, seed=None):
         lib = _lib.load()
         N, Fdim = x.shape

@@ -1237,6 +1237,93 @@ int ampconv_tsne_step(const float *y_in, float *y_out, float *update, float *gai
                       float exaggeration, float momentum, float learning_rate, float min_gain, double *error,
                       void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- UMAP -------------------------------------------------------------------------
+ * The kernels under ampnet_amd.umap (csrc/umap.hip): the reference's visualization/UMAP_testing.ipynb,
+ * umap.UMAP(n_neighbors=15, n_components=2, min_dist=0.1, metric='euclidean').fit_transform(x), and its UMAP featuriser
+ * (src/ampnet/utils/preprocess.py: n_components=30 on x.T).  Added without a version change: no existing argument list
+ * changes.
+ *
+ * WHAT ampnet_amd.umap COMPUTES.  This text and the fp64 model in tests/umap_reference.py ARE the specification: the
+ * semantics are umap-learn 0.5's defaults (metric='euclidean', set_op_mix_ratio=1, local_connectivity=1, spread=1,
+ * repulsion_strength gamma = 1, negative_sample_rate=5, initial_alpha=1), restated here because umap-learn is not a
+ * dependency; PARITY WITH umap-learn's BITS IS UNPINNED, and two things differ on purpose: the epoch is synchronous
+ * (below) and the start is PCA, not spectral.
+ *   neighbours: k = n_neighbors columns per sample, column 0 the sample itself at distance 0, columns 1 .. k - 1 its
+ *   k - 1 nearest other samples as Euclidean distances (float32 sqrt of the squared ones), nearest first;
+ *   2 <= k <= min(M, AMPCONV_UMAP_MAX_K).
+ *   calibration (smooth_knn_dist), per row in fp64: target = log2(k); rho = the smallest distance of the row that is
+ *   > 0, or 0; lo = 0, hi = inf, mid = 1, at most 64 rounds of
+ *     psum = sum_{j = 1 .. k-1} (d_j - rho > 0 ? exp(-(d_j - rho) / mid) : 1);  stop if |psum - target| < 1e-5;
+ *     psum > target: hi = mid, mid = (lo + hi) / 2;  else lo = mid, mid = 2 mid while hi is infinite, else (lo + hi) / 2;
+ *   sigma = mid, floored: rho > 0: sigma = max(sigma, 1e-3 x the mean of the row's k distances, column 0 included);
+ *   rho = 0: sigma = max(sigma, 1e-3 x the mean of all M k distances).
+ *   memberships (float32 [M, k]): 0 where the neighbour is the row itself; 1 where d - rho <= 0 or sigma = 0; else
+ *   exp(-(d - rho) / sigma), evaluated in fp64 and rounded once.
+ *   fuzzy union: the CSR of W = P + P^T - P o P^T for P[i, idx[i, j]] = membership[i, j]: indices ascend within a
+ *   row, exact zeros are no entries, each value is (p + q) - p q in float32 from the two float32 memberships (a missing
+ *   one is 0): the expression is symmetric in p and q, so W[i, j] and W[j, i] are THE SAME BITS.
+ *   curve: (a, b) = the least-squares fit of 1 / (1 + a x^(2b)) to y(x) = 1 for x < min_dist, else
+ *   exp(-(x - min_dist) / spread), on x = linspace(0, 3 spread, 300) (a ~ 1.5769, b ~ 0.8951 for the defaults).
+ *   schedule: n_epochs defaults to 500 for M <= 10000, else 200; entries with w < max(w) / n_epochs are dropped (float32
+ *   division); per remaining DIRECTED entry e (its position in the CSR) eps_e = max(w) / w_e (float32) and the state
+ *   next_e = eps_e, nextneg_e = eps_e / 5 (float32), drawn_e = 0 (int32).
+ *   epoch n (SYNCHRONOUS: reads Y_in, writes Y_out, alpha = 1 - n / n_epochs): entry e = (j -> k) FIRES if next_e <= n.
+ *     attraction: d2 = |Y_j - Y_k|^2, c = d2 > 0 ? -2 a b d2^(b-1) / (a d2^b + 1) : 0, g = clip(c (Y_j - Y_k), +-4) per
+ *     coordinate; row j receives 2 g alpha.  The factor 2 is umap-learn's move_other: the mirrored entry (k -> j) has
+ *     the same weight bits, hence the same eps and firing history, and with the positions frozen for the epoch its
+ *     update of its tail is exactly this g -- so every row gathers over its own CSR row, nothing is scattered and
+ *     there are no atomics.  umap-learn's loop is sequential (or Hogwild) and in place; this one is not.
+ *     then next_e += eps_e; epn = eps_e / 5; m = int((n - nextneg_e) / epn), clamped to [0, AMPCONV_UMAP_MAX_NEGATIVES]
+ *     (float32 subtraction and IEEE division, truncated); for p < m: s = draw(seed, e, drawn_e + p) % M with
+ *     draw(seed, a, b) = splitmix64(seed ^ splitmix64(a * 0x100000001B3 + b)) (uint64, wrapping: the library's stream),
+ *     d2 = |Y_j - Y_s|^2, c = d2 > 0 ? 2 gamma b / ((0.001 + d2) (a d2^b + 1)) : 0, row j receives
+ *     clip(c (Y_j - Y_s), +-4) alpha (nothing if c = 0); then drawn_e += m, nextneg_e += m epn (the product rounded to
+ *     float32, then the sum).  Firing decisions, m and the drawn ids are integer-exact.
+ *   start: PCA scores (there is NO spectral start) or a given [M, n_components] tensor, every column mapped to [0, 10]:
+ *   10 (y - min) / (max - min), as umap-learn does before its optimiser.
+ *
+ * ampconv_umap_memberships: idx [M, k] int64 (row stride ldi >= k) and dist [M, k] fp32 (row stride ldd >= k), both
+ * read in place; memb [M, k] fp32 (row stride k), sigma and rho [M] fp64.  One wave per row; psum and the row's sum
+ * are butterflies over the lanes, the sum of all distances is the rows' sums added by lane t taking t, t + 256, ...
+ * and a binary tree (s[t] += s[t + o], o = 128 .. 1): fixed orders, two calls give the same bits, and they differ from
+ * sequential sums by fp64 rounding only.  Workspace: ampconv_umap_memberships_workspace_bytes(M), 8-byte aligned.
+ *
+ * ampconv_umap_epoch: one epoch, one launch sequence, nothing read back.  y_in, y_out [M, dim] fp32 dense and 8-byte
+ * aligned, different buffers; 2 <= dim <= AMPCONV_UMAP_MAX_DIM (dim = 2 has its own instantiation with 8-byte loads);
+ * the CSR (indptr [M + 1], indices [nnz] int64; a column outside [0, M) is clamped, positions outside [0, nnz] likewise)
+ * with eps [nnz] fp32 and the state next, nextneg [nnz] fp32, drawn [nnz] int32 updated in place.  d2 by FMAs over the
+ * coordinates in order, d2^b = exp2(b log2(d2)) in fp32, one division per coefficient (ampconv_umap_coefficients
+ * evaluates exactly these two functions on an array of d2, for measuring their error).  The sum of a row: the row is
+ * cut into groups of 64 entries from its start; lane l of a wave adds entry l's attraction, then its negatives in
+ * order, in fp32 (FMAs with alpha); a butterfly adds the lanes; the groups are added in order in fp64 and
+ * y_out = fp32(y_in + sum) with the addition in fp64.  A row longer than AMPCONV_UMAP_PART entries is cut into parts
+ * of that length whose groups separate waves compute and store; the order of the additions is the same, so THE RESULT
+ * DOES NOT DEPEND ON THE PART LENGTH -- ampconv_umap_epoch_split takes it as an argument (a multiple of 64 in
+ * [64, 2^24]) for tests to show that.  Workspace: ampconv_umap_epoch_workspace_bytes(M, nnz, dim), 8-byte aligned:
+ * (nnz / 64 + M + 1) dim floats; nothing of size M^2 exists.
+ * AMPCONV_E_BADARG (nothing launched): a NULL or misaligned pointer, y_in == y_out, M outside [2, AMPCONV_UMAP_MAX_M]
+ * (the epoch takes M = 1), k outside [2, min(M, AMPCONV_UMAP_MAX_K)], a stride below k, dim or part out of range,
+ * epoch outside [0, 2^24].  AMPCONV_E_WORKSPACE: a NULL or short workspace.  */
+#define AMPCONV_UMAP_MAX_K 256
+#define AMPCONV_UMAP_MAX_M (1 << 24)
+#define AMPCONV_UMAP_MAX_DIM 32
+#define AMPCONV_UMAP_PART 1024
+#define AMPCONV_UMAP_MAX_NEGATIVES 65536
+size_t ampconv_umap_memberships_workspace_bytes(int64_t M);
+int ampconv_umap_memberships(const int64_t *idx, int64_t ldi, const float *dist, int64_t ldd, int64_t M, int k, float *memb,
+                             double *sigma, double *rho, void *workspace, size_t workspace_bytes, void *stream);
+int ampconv_umap_coefficients(const float *d2, int64_t n, float a, float b, float gamma, float *attract, float *repel,
+                              void *stream);
+size_t ampconv_umap_epoch_workspace_bytes(int64_t M, int64_t nnz, int dim);
+int ampconv_umap_epoch(const float *y_in, float *y_out, int64_t M, int dim, const int64_t *indptr, const int64_t *indices,
+                       int64_t nnz, const float *eps, float *next, float *nextneg, int32_t *drawn, float a, float b,
+                       float gamma, float alpha, int epoch, uint64_t seed, void *workspace, size_t workspace_bytes,
+                       void *stream);
+int ampconv_umap_epoch_split(const float *y_in, float *y_out, int64_t M, int dim, const int64_t *indptr,
+                             const int64_t *indices, int64_t nnz, const float *eps, float *next, float *nextneg,
+                             int32_t *drawn, float a, float b, float gamma, float alpha, int epoch, uint64_t seed, int part,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
