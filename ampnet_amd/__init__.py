@@ -25,6 +25,7 @@ from .knn import knn, knn_classify, knn_graph
 from .pca import PCAResult, pca
 from .tsne import TSNEResult, neighbor_preservation, tsne
 from .umap import UMAPResult, umap
+from .spring import SpringLayout, SpringResult, spring_layout
 
 __all__ = ['AMPConv', 'InvalidConfiguration', 'EdgeCSR', 'graph_cache', 'distributed', 'AMPGCN', 'FeatureTokens',
            'GraphSAINTRandomWalkSampler', 'NodePartition', 'PartitionedAMPConv', 'GraphedAMPConv', 'AttentionHeatmap', 'top_features',
@@ -32,4 +33,5 @@ __all__ = ['AMPConv', 'InvalidConfiguration', 'EdgeCSR', 'graph_cache', 'distrib
            'NormTokenReadout', 'TokenLayerNorm', 'norm_act_dropout', 'norm_act_dropout_pool', 'FusedAdam',
            'TensorStats', 'tensor_stats', 'GCNConv', 'GCN', 'gcn_norm', 'gcn_aggregate', 'gcn_input_linear',
            'pair_loss', 'PairLoss', 'walk_pairs', 'knn', 'knn_graph', 'knn_classify', 'pca', 'PCAResult',
-           'tsne', 'TSNEResult', 'neighbor_preservation', 'umap', 'UMAPResult']
+           'tsne', 'TSNEResult', 'neighbor_preservation', 'umap', 'UMAPResult',
+           'spring_layout', 'SpringResult', 'SpringLayout']

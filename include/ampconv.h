@@ -1324,6 +1324,89 @@ int ampconv_umap_epoch_split(const float *y_in, float *y_out, int64_t M, int dim
                              int32_t *drawn, float a, float b, float gamma, float alpha, int epoch, uint64_t seed, int part,
                              void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Spring layout ----------------------------------------------------------------
+ * The kernels under ampnet_amd.spring (csrc/spring.hip): the reference's picture of a graph --
+ * synthetic_benchmark/synthetic_xor.py (plot_graph: nx.spring_layout(G)) and
+ * visualization/visualize_graphsaint_subgraphs.py (nx.draw(g), whose default layout is the same).  Added without a
+ * version change: no existing argument list changes.
+ *
+ * WHAT ampnet_amd.spring_layout COMPUTES.  This text and the fp64 model in tests/spring_reference.py ARE the
+ * specification: networkx 3.4.2's spring_layout (drawing/layout.py: _fruchterman_reingold,
+ * _sparse_fruchterman_reingold, rescale_layout), restated here because networkx is not a dependency.  Parity with
+ * networkx's VALUES is pinned by the fixtures under tests/golden/spring; parity with its bits is not.  With N nodes,
+ * dim in {2, 3}, the adjacency A as a CSR with float32 weights and positions y [N, dim] float32:
+ *   optimal distance: k = 1 / sqrt(N) unless given; with fixed nodes and no k, dom_size / sqrt(N), dom_size = the
+ *   largest coordinate of the given positions, 1 if that is 0.
+ *   temperature: t0 = 0.1 max(extent of column 0, extent of column 1) of the start -- the first two columns only, as
+ *   networkx has it -- and dt = t0 / (iterations + 1), both fp64.
+ *   iteration (SYNCHRONOUS: reads y_in, writes y_out):
+ *     rep_i = sum_j (y_i - y_j) / max(|y_i - y_j|^2, 1e-4f) over ALL j: a coincident point and j = i contribute exactly
+ *     0, so no index is excluded;
+ *     att_i = sum over the entries e = (i -> j) of row i of w_e max(sqrt(|y_i - y_j|^2), 0.01f) (y_i - y_j);
+ *     disp_i = k^2 rep_i - att_i / k (fp64); len_i = |disp_i|, replaced by 0.1 where it is < 0.01;
+ *     delta_i = fp32(disp_i (t / len_i)), zero for fixed nodes; y_out = y_in + delta (fp32);
+ *     then t -= dt, ran += 1, done = sqrt(sum delta^2) / N < threshold.
+ *   start: a given tensor, or uniform [0, 1): y[i, c] = (draw(seed, i, c) >> 40) 2^-24 with the library's stream,
+ *   draw(seed, a, b) = splitmix64(seed ^ splitmix64(a * 0x100000001B3 + b)) (uint64, wrapping); with fixed nodes and
+ *   partial positions the others are rand dom_size + center, networkx's rule.
+ *   finish (no fixed nodes, scale not None): subtract the fp64 column means, multiply by scale / max|y| (skipped if the
+ *   maximum is 0), add center.
+ *
+ * DEVICE STATE.  ampconv_spring_state: {double t, double dt, int64 ran, int64 done}, 32 bytes on the device, 8-byte
+ * aligned; the host reads nothing during the layout.  A step entered with done != 0 copies y_in to y_out and changes
+ * nothing else (the repulsion, given the state, launches and returns at once), so a fixed sequence of `iterations`
+ * steps reproduces networkx's `break`.
+ *
+ * ampconv_spring_start: y [N, dim] fp32 dense = the uniform start above.
+ *
+ * ampconv_spring_repulsion: y [N, dim] fp32 dense, 8-byte aligned; rep [N, dim] fp64.  Pair arithmetic is fp32:
+ * y_i - y_j, |.|^2 by FMAs over the coordinates in order from 0, max with 1e-4f, one v_rcp_f32 (1 ulp), one FMA per
+ * coordinate into the sum -- k^2 is applied by the step, after the sums.  For row i the sums run over the keys j in
+ * ascending order in fp32 for a run of AMPCONV_SPRING_RUN keys (runs start at multiples of it), the runs of a chunk are
+ * added in order in fp64, the chunks in order in fp64.  A chunk is AMPCONV_SPRING_CHUNK
+ * ceil(ceil(N / AMPCONV_SPRING_CHUNK) / 64) keys: a function of N alone, so is the launch.  No atomics: two calls give
+ * the same bits.  |rep - exact| <= (AMPCONV_SPRING_RUN + 16) 2^-24 sum_j |term_j| per coordinate.  state (NULL: always
+ * computed): with state->done != 0 rep is left as it is.  Workspace: ampconv_spring_repulsion_workspace_bytes(N, dim),
+ * 8-byte aligned: the chunks' fp64 sums [chunk][dim][N], at most 64 chunks (37 MB at 96 000 points, dim 2).
+ *
+ * ampconv_spring_step: one iteration from rep as ampconv_spring_repulsion left it.  y_in, y_out [N, dim] fp32 dense,
+ * 8-byte aligned, different buffers; the CSR of A (indptr [N + 1], indices [nnz] int64; a column outside [0, N) is
+ * clamped, positions outside [0, nnz] likewise); val [nnz] fp32, NULL: every weight is 1; fixed [N] bytes, nonzero: the
+ * node does not move, NULL: none is fixed.  The attraction of a row: the row is cut into groups of 64 entries from its
+ * start, lane l of a wave takes entry l of the group in fp32 (the pair arithmetic above, sqrt correctly rounded, the
+ * weight times the clamped distance, one FMA per coordinate), a butterfly adds the lanes, the groups are added in order
+ * in fp64.  A row longer than AMPCONV_SPRING_PART entries is cut into parts of that length whose groups separate waves
+ * compute and store; the order of the additions is the same, so THE RESULT DOES NOT DEPEND ON THE PART LENGTH --
+ * ampconv_spring_step_split takes it as an argument (a multiple of 64 in [64, 2^24]) for tests to show that.
+ * |att - exact| <= 16 2^-24 sum_e |term_e| per coordinate.  The rows' sum delta^2 (fp64, of the float32 delta) is added
+ * by lane t of one workgroup taking the rows t, t + 256, ... in order and a binary tree (s[t] += s[t + o],
+ * o = 128 .. 1); that workgroup then moves the state.  Workspace: ampconv_spring_step_workspace_bytes(N, nnz, dim),
+ * 8-byte aligned: (nnz / 64 + N + 1) dim floats and N doubles.
+ * AMPCONV_E_BADARG (nothing launched): a NULL or misaligned pointer, y_in == y_out, N outside
+ * [1, AMPCONV_SPRING_MAX_N], dim outside {2, 3}, nnz < 0, k not positive and finite, part out of range.
+ * AMPCONV_E_WORKSPACE: a NULL or short workspace.  */
+#define AMPCONV_SPRING_MAX_N (1 << 24)
+#define AMPCONV_SPRING_RUN 256
+#define AMPCONV_SPRING_TILE 1024
+#define AMPCONV_SPRING_CHUNK 4096
+#define AMPCONV_SPRING_PART 1024
+typedef struct {
+  double t, dt;
+  int64_t ran, done;
+} ampconv_spring_state;
+int ampconv_spring_start(float *y, int64_t N, int dim, uint64_t seed, void *stream);
+size_t ampconv_spring_repulsion_workspace_bytes(int64_t N, int dim);
+int ampconv_spring_repulsion(const float *y, int64_t N, int dim, double *rep, const ampconv_spring_state *state,
+                             void *workspace, size_t workspace_bytes, void *stream);
+size_t ampconv_spring_step_workspace_bytes(int64_t N, int64_t nnz, int dim);
+int ampconv_spring_step(const float *y_in, float *y_out, int64_t N, int dim, const int64_t *indptr, const int64_t *indices,
+                        const float *val, int64_t nnz, const uint8_t *fixed, const double *rep, double k, double threshold,
+                        ampconv_spring_state *state, void *workspace, size_t workspace_bytes, void *stream);
+int ampconv_spring_step_split(const float *y_in, float *y_out, int64_t N, int dim, const int64_t *indptr,
+                              const int64_t *indices, const float *val, int64_t nnz, const uint8_t *fixed, const double *rep,
+                              double k, double threshold, ampconv_spring_state *state, int part, void *workspace,
+                              size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
