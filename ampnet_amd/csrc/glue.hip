@@ -9,6 +9,7 @@
 // All four operations stream their tensors once: 16 bytes per lane, a wave's lanes on consecutive 16-byte pieces,
 // four loads in flight per lane and stream, no LDS.  Bases that are not 16-byte aligned and rows that are no multiple
 // of 16 bytes (the XOR toy: L = 2, D = 3) take the element-wise kernels at the end of each section.
+// The launch arithmetic (vec / scalar, capped_blocks, pool_grid) is mirrored and pinned by tests/test_gpu_glue_kernels.py.
 #include "site_common.h"
 
 namespace {

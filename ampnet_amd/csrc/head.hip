@@ -19,6 +19,7 @@
 // METRICS.  Per-mask loss sums are 64-bit fixed point (AMPCONV_HEAD_LOSS_SHIFT), counts are integers; both are added
 // with integer atomics into a per-call scratch, which a one-wave kernel then adds to the caller's running buffer and
 // turns into the fp32 loss: order-independent, so bitwise reproducible.
+// dispatch, make_geom (with its LDS byte count) and grid_of are mirrored and pinned by tests/test_gpu_head_kernels.py.
 #include <type_traits>
 
 #include "common.h"

@@ -11,6 +11,7 @@
 // bases run the same kernels on one-element pieces, a wave per token.
 // dgamma, dbeta: per-lane register sums over the group's tokens, a butterfly over the groups of a wave, the 4 waves of
 // a workgroup in wave order through LDS into the workgroup's [2, D] slot, then norm_reduce_slots: no atomics.
+// row_shape, tokens_per_step and grid_of are mirrored and pinned by tests/test_gpu_norm_kernels.py.
 #include "site_common.h"
 
 namespace {

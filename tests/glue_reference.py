@@ -32,6 +32,8 @@ def fields(seed, n):
 def keep_mask(seed, thr, shape):
     """Boolean array of `shape` (row-major = flat index i): True where the element is kept (field >= threshold)."""
     n = int(np.prod(shape))
+    if thr == 0:                                                 # every field is >= 0
+        return np.ones(shape, dtype=bool)
     return (fields(seed, n) >= _U(thr)).reshape(shape)
 
 
@@ -54,14 +56,17 @@ def act_slope(x, activation):
     return np.ones_like(x)
 
 
-def act_dropout_fwd(x, activation, seed, p):
+def act_dropout_fwd(x, activation, seed, p, keep=None):
+    """keep: keep_mask(seed, threshold of p, x.shape) where the caller already has it (one mask serves many calls)."""
     thr, scale = mask_params(p)
-    return np.where(keep_mask(seed, thr, x.shape), act(x, activation) * float(scale), 0.0)
+    keep = keep_mask(seed, thr, x.shape) if keep is None else keep
+    return np.where(keep, act(x, activation) * float(scale), 0.0)
 
 
-def act_dropout_bwd(x, dy, activation, seed, p):
+def act_dropout_bwd(x, dy, activation, seed, p, keep=None):
     thr, scale = mask_params(p)
-    return np.where(keep_mask(seed, thr, x.shape), np.asarray(dy, np.float64) * float(scale) * act_slope(x, activation), 0.0)
+    keep = keep_mask(seed, thr, x.shape) if keep is None else keep
+    return np.where(keep, np.asarray(dy, np.float64) * float(scale) * act_slope(x, activation), 0.0)
 
 
 def pool_fwd(x, L, D, activation, pooling, seed, p):

@@ -3,7 +3,8 @@ tests/glue_reference.py, against torch autograd, and inside the whole model agai
 
 Shapes (N, L, D): (5, 3, 4) fewer rows than waves and a row shorter than one wave's span; (257, 40, 100) a ragged last
 workgroup, 1000 16-byte pieces per row; (64, 20, 128); (33, 1, 128) a single token; (64, 2, 3) the XOR toy's rows, which
-no 16-byte piece divides (element-wise kernels).  fp32 everywhere, bf16 where D % 8 == 0.
+no 16-byte piece divides (element-wise kernels).  fp32 everywhere, bf16 where D % 8 == 0.  The launch paths these shapes do
+not reach (grid stride, tile and unroll remainders, unaligned bases) are on the ladders of tests/test_gpu_glue_kernels.py.
 Tolerances: fp32 the project's flat atol 1e-5, rtol 1e-4; bf16 storage atol 2e-2, rtol 2e-2 (tests/test_gpu_parity.py,
 test_bf16_storage)."""
 import functools

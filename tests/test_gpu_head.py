@@ -5,7 +5,8 @@ whole model.
 Shapes (N, D, C): (1, 3, 2) a single row; (64, 3, 2) the XOR model, element-wise path; (257, 100, 7) the class defaults,
 ragged rows and a ragged last tile; (48, 128, 7) the Cora fixture; (33, 128, 1) one class: the log-probabilities are
 exactly 0; (20011, 256, 64) many workgroups: the cross-workgroup reduction, the class limit and W read from global memory;
-(0, 128, 7) empty.  fp32 everywhere, bf16 pooled where D % 8 == 0.
+(0, 128, 7) empty.  fp32 everywhere, bf16 pooled where D % 8 == 0.  Row passes, class chunks, the home of W and the rows
+per tile beyond these shapes are on the ladders of tests/test_gpu_head_kernels.py.
 Tolerances: the project's flat atol 1e-5, rtol 1e-4 on log-probabilities and fp32 dpooled; the scaled bar (labels gW, gb)
 on dW and db; bf16 dpooled atol = rtol = 2e-2 (tests/test_gpu_glue.py); counts exact."""
 import functools

@@ -5,7 +5,8 @@ nn.LayerNorm's functional form.
 Shapes (N, L, D): (5, 3, 4) fewer tokens than one wave's groups, a one-piece row; (257, 40, 100) 25 pieces in a 32-lane
 group (masked lanes), a ragged last workgroup; (64, 20, 128) whole pieces, no masked lanes; (33, 1, 768) several pieces
 per lane, one token per node; (3, 2, 1024) the widest row; (64, 2, 3) the element-wise path.  fp32 everywhere, bf16
-where D % 8 == 0.
+where D % 8 == 0.  Every other (G, K, U) of norm.hip, the grid stride and the slot counts are on the ladders of
+tests/test_gpu_norm_kernels.py.
 Tolerances: y, pooled, dx at the project's flat atol 1e-5, rtol 1e-4; the weight and bias gradients (sums over all
 tokens) under labels that name a parameter gradient, i.e. atol scaled by their magnitude; bf16 storage atol 2e-2,
 rtol 2e-2."""
