@@ -37,6 +37,15 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
   x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
   return x ^ (x >> 31);
 }
+// the library's stream (include/ampconv.h): uint64, wrapping, all 64 bits of the seed
+__device__ __forceinline__ uint64_t draw(uint64_t seed, uint64_t a, uint64_t b) {
+  return splitmix64(seed ^ splitmix64(a * 0x100000001B3ull + b));
+}
+
+// workspace sections start on 256 bytes; argument checks of the entry points (a null pointer is not aligned)
+static inline size_t pad256(size_t x) { return (x + 255) & ~(size_t)255; }
+static inline bool aligned4(const void *p) { return p && (uintptr_t)p % 4 == 0; }
+static inline bool aligned8(const void *p) { return p && (uintptr_t)p % 8 == 0; }
 
 static inline bool view_ok(const ampconv_view_t &v) { return v.ptr != nullptr; }
 
@@ -70,6 +79,17 @@ __device__ __forceinline__ void wave_record_absmax(float *p, float m) {
 __device__ __forceinline__ float wave_sum(float x) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  return x;
+}
+// the same butterflies in fp64: every lane ends with the same bits
+__device__ __forceinline__ double wave_sum_f64(double x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  return x;
+}
+__device__ __forceinline__ double wave_min_f64(double x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x = fmin(x, __shfl_xor(x, o, 64));
   return x;
 }
 

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(64) void sample_present_kernel(const float *__restr
     return;
   }
   for (int l = lane; l < L; l += 64) {
-    const uint64_t r = splitmix64(seed ^ splitmix64((uint64_t)n * 0x100000001B3ull + (uint64_t)l));
+    const uint64_t r = draw(seed, (uint64_t)n, (uint64_t)l);
     int k = (int)(r % (uint64_t)total);               // rank among the present features
     int c = 0;
     while (c + 1 < nchunk && prefix[c + 1] <= k) ++c;

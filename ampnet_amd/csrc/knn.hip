@@ -319,7 +319,7 @@ int launch_kq(const KnnArgs &a, dim3 grid, hipStream_t stream) {
 extern "C" size_t ampconv_knn_workspace_bytes(int64_t Q, int64_t S, int64_t N, int D, int k) {
   if (Q <= 0 || S < 0 || N < 0 || D < 1 || D > AMPCONV_KNN_MAX_D || k < 1 || k > AMPCONV_KNN_MAX_K) return 0;
   if (Q > kMaxCount || S > kMaxCount || N > kMaxCount) return 0;
-  return up256((size_t)N * sizeof(float)) + up256((size_t)part_rows(Q, S) * (size_t)k * sizeof(unsigned long long));
+  return pad256((size_t)N * sizeof(float)) + pad256((size_t)part_rows(Q, S) * (size_t)k * sizeof(unsigned long long));
 }
 
 extern "C" int ampconv_knn(const void *X, int64_t N, int D, int64_t ldx, const int64_t *query, int64_t Q,
@@ -349,7 +349,7 @@ extern "C" int ampconv_knn(const void *X, int64_t N, int D, int64_t ldx, const i
   a.tiles = sp.tiles; a.tiles_per_split = sp.per; a.k = k; a.metric = metric; a.exclude = exclude_self != 0;
   float *aux = (float *)workspace;
   a.aux = metric == AMPCONV_KNN_DOT ? nullptr : aux;
-  a.part = sp.n > 1 ? (unsigned long long *)((char *)workspace + up256((size_t)N * sizeof(float))) : nullptr;
+  a.part = sp.n > 1 ? (unsigned long long *)((char *)workspace + pad256((size_t)N * sizeof(float))) : nullptr;
   a.idx = idx; a.score = score; a.oob = oob;
 
   hipMemsetAsync(oob, 0, sizeof(int32_t), stream);

@@ -401,13 +401,13 @@ BwdLayout bwd_layout(int64_t B, int64_t S, int D) {
   const size_t rb = (size_t)dq_of(D) * sizeof(float);
   l.a = stream_split(B, S, rb);
   l.n = stream_split(S, B, rb);
-  l.off_p = up256((size_t)l.a.n * B * rb);
-  l.off_n = l.off_p + up256((size_t)B * rb);
-  l.bytes = l.off_n + up256((size_t)l.n.n * S * rb);
+  l.off_p = pad256((size_t)l.a.n * B * rb);
+  l.off_n = l.off_p + pad256((size_t)B * rb);
+  l.bytes = l.off_n + pad256((size_t)l.n.n * S * rb);
   return l;
 }
 size_t fwd_bytes(int64_t B, int64_t S) {
-  return up256((size_t)stream_split(B, S, 0).n * B * sizeof(float)) * 2 + up256((size_t)B * sizeof(float));
+  return pad256((size_t)stream_split(B, S, 0).n * B * sizeof(float)) * 2 + pad256((size_t)B * sizeof(float));
 }
 
 template <int KQ4, int MODE>
@@ -472,7 +472,7 @@ extern "C" int ampconv_pair_loss_fwd(const void *Z, int64_t N, int D, int64_t ld
   if (!aff || !neg_term || !workspace) return AMPCONV_E_BADARG;
   if (workspace_bytes < fwd_bytes(B, S)) return AMPCONV_E_WORKSPACE;
   const Split sp = stream_split(B, S, 0);
-  const size_t part = up256((size_t)sp.n * B * sizeof(float));
+  const size_t part = pad256((size_t)sp.n * B * sizeof(float));
   float *pm = (float *)workspace, *ps = (float *)((char *)workspace + part), *wl = (float *)((char *)workspace + 2 * part);
 
   hipMemsetAsync(oob, 0, sizeof(int32_t), stream);

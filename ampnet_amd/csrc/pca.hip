@@ -358,7 +358,7 @@ void set_rows(A &a, const void *x, int W, int64_t ldx, int dtype) {
 
 extern "C" size_t ampconv_pca_shift_workspace_bytes(int64_t R, int W, int axis) {
   if (R < 1 || R > kMaxRows || W < 1 || W > AMPCONV_PCA_MAX_W || (axis != 0 && axis != 1)) return 0;
-  return axis == 0 ? up256((size_t)mean_split(R).n * (size_t)W * sizeof(double)) : 0;
+  return axis == 0 ? pad256((size_t)mean_split(R).n * (size_t)W * sizeof(double)) : 0;
 }
 
 extern "C" int ampconv_pca_shift(const void *x, int64_t R, int W, int64_t ldx, int axis, float *out, void *workspace,
@@ -387,7 +387,7 @@ extern "C" int ampconv_pca_gram_splits(int64_t R, int W) {
 
 extern "C" size_t ampconv_pca_gram_workspace_bytes(int64_t R, int W) {
   if (R < 1 || R > kMaxRows || W < 1 || W > AMPCONV_PCA_MAX_W) return 0;
-  return up256((size_t)gram_split(R, W).n * (size_t)W * (size_t)W * sizeof(double));
+  return pad256((size_t)gram_split(R, W).n * (size_t)W * (size_t)W * sizeof(double));
 }
 
 extern "C" int ampconv_pca_gram(const void *x, int64_t R, int W, int64_t ldx, const float *row_shift,

@@ -96,4 +96,3 @@ static inline Split stream_split(int64_t nfixed, int64_t nstream, size_t row_byt
   s.n = std::max(1, (s.tiles + s.per - 1) / s.per);
   return s;
 }
-static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }

@@ -28,7 +28,7 @@ __global__ void random_walk_kernel(const int32_t *__restrict__ cscptr, const int
   for (int t = 0; t < walk_length; ++t) {
     const int beg = cscptr[cur], deg = cscptr[cur + 1] - beg;
     if (deg > 0) {
-      const uint64_t r = splitmix64(seed ^ splitmix64((uint64_t)b * 0x100000001B3ull + (uint64_t)t));
+      const uint64_t r = draw(seed, (uint64_t)b, (uint64_t)t);
       cur = crow[beg + (int)(r % (uint64_t)deg)];
     }
     w[t + 1] = cur;

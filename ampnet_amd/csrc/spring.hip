@@ -3,26 +3,16 @@
 // stopping rule, with the state of the schedule on the device.  The adjacency (a library sort), the start's extent and
 // the final rescaling are the Python side's (ampnet_amd/spring.py).
 //
-// Repulsion.  tsne_repulsion_kernel's N-body pattern: a workgroup of 256 lanes owns AMPCONV_SPRING_TILE = 1024 query
-// points (four per lane: four independent reciprocals in flight, a key is read once for four pairs) and one chunk of
-// keys.  Keys are read at a wave-uniform address (scalar loads: no LDS, no vector memory traffic) and enter the VALU as
-// scalar operands.  Per pair and dim = 2: two subtractions, a product and an FMA for d^2, a max, v_rcp_f32, two FMAs --
-// all but the max and the reciprocal packed over two query points, five instructions per pair;
-// k^2 is applied by the step after the sums, so the pair carries no other factor.  j = i needs no compare: its
-// difference is exactly 0 and 0 / 1e-4 adds nothing.  The fp32 sums live for a run of AMPCONV_SPRING_RUN keys, in key
-// order, then go into fp64 registers; a chunk's fp64 sums go to the workspace [chunk][dim][N] and
-// spring_repulsion_fold_kernel adds the chunks in order.  The chunk length is a function of N alone, so the bits do not
-// depend on how the work is spread.
+// Repulsion.  The chunked N-body pass of layout_common.h with dim planes.  Per pair and dim = 2: two subtractions, a
+// product and an FMA for d^2, a max, v_rcp_f32, two FMAs -- all but the max and the reciprocal packed over two query
+// points, five instructions per pair; k^2 is applied by the step after the sums, so the pair carries no other factor.
+// j = i needs no compare: its difference is exactly 0 and 0 / 1e-4 adds nothing.
 //
-// Step.  umap_epoch_kernel's gather: one wave per row, the row cut into groups of 64 entries from its start, lane l
-// takes entry l of the group, a butterfly adds the lanes, the groups are added in order in fp64.  A row longer than
-// `part` entries is cut into parts whose groups spring_parts_kernel computes and stores (one wave per window of `part`
-// positions of the entry array: at most two parts start in a window), and the row's wave adds the stored groups in the
-// same order: the part length decides who computes a group, never what is added to what.  The lane-0 tail is the
-// displacement, its length with networkx's floor, the move and the row's share of sum delta^2.  spring_finish_kernel
-// (one workgroup) adds the rows' shares in a fixed order and moves the state: t, ran, done.  A launch sequence entered
-// with done != 0 copies y_in to y_out and leaves everything else as it is.
-#include "common.h"
+// Step.  layout_common.h's grouped gather with its long-row scheme; an entry adds max(|d|, 0.01) w d (SpringEntry).
+// The lane-0 tail is the displacement, its length with networkx's floor, the move and the row's share of sum delta^2.
+// spring_finish_kernel (one workgroup) adds the rows' shares in a fixed order and moves the state: t, ran, done.  A
+// launch sequence entered with done != 0 copies y_in to y_out and leaves everything else as it is.
+#include "layout_common.h"
 
 #include <cmath>
 
@@ -31,9 +21,7 @@ namespace {
 constexpr int kRun = AMPCONV_SPRING_RUN;
 constexpr int kTile = AMPCONV_SPRING_TILE;
 constexpr int kChunk0 = AMPCONV_SPRING_CHUNK;
-constexpr int kGroup = 64;
 constexpr int kQ = kTile / 256;              // query points per lane
-constexpr int kMaxChunks = 64;
 constexpr float kMinDist = 0.01f, kMinDist2 = 1e-4f;     // networkx's clip of the distance, and its square
 static_assert(kChunk0 % kRun == 0 && kTile % 512 == 0 && AMPCONV_SPRING_PART % kGroup == 0 && kGroup == AMPCONV_WAVE,
               "lane maps of this file");
@@ -41,48 +29,16 @@ static_assert(sizeof(ampconv_spring_state) == 32, "the state is four 8-byte word
 
 typedef ampconv_spring_state State;
 
-inline size_t pad256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-template <int D>
-__device__ __forceinline__ void load_point(const float *__restrict__ y, int64_t j, float (&v)[D]) {
-  if constexpr (D == 2) {
-    const float2 t = reinterpret_cast<const float2 *>(y)[j];
-    v[0] = t.x; v[1] = t.y;
-  } else {
-#pragma unroll
-    for (int c = 0; c < D; ++c) v[c] = y[j * D + c];
-  }
-}
-
-// d = a - b per coordinate; returns |d|^2 by FMAs over the coordinates in order
-template <int D>
-__device__ __forceinline__ float difference(const float (&a)[D], const float (&b)[D], float (&d)[D]) {
-  float d2 = 0.f;
-#pragma unroll
-  for (int c = 0; c < D; ++c) {
-    d[c] = a[c] - b[c];
-    d2 = fmaf(d[c], d[c], d2);
-  }
-  return d2;
-}
-
 // ----------------------------------------------------------------------------------------------------------- start
 __global__ __launch_bounds__(256) void spring_start_kernel(float *__restrict__ y, int64_t N, int dim, uint64_t seed) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= N * dim) return;
   const uint64_t i = (uint64_t)(e / dim), c = (uint64_t)(e % dim);
-  const uint64_t r = splitmix64(seed ^ splitmix64(i * 0x100000001B3ull + c));
+  const uint64_t r = draw(seed, i, c);
   y[e] = (float)(r >> 40) * 0x1p-24f;                                // 24 bits: exact in fp32, [0, 1)
 }
 
 // ------------------------------------------------------------------------------------------------------- repulsion
-// keys per chunk, from N alone: AMPCONV_SPRING_CHUNK times ceil(ceil(N / AMPCONV_SPRING_CHUNK) / 64): at most 64 chunks
-int chunk_keys(int64_t N) {
-  const int64_t c0 = (N + kChunk0 - 1) / kChunk0;
-  return kChunk0 * (int)((c0 + kMaxChunks - 1) / kMaxChunks);
-}
-int chunk_count(int64_t N) { return (int)((N + chunk_keys(N) - 1) / chunk_keys(N)); }
-
 // Two query points ride in the two halves of a packed fp32 register pair (v_pk_add_f32, v_pk_mul_f32, v_pk_fma_f32); the
 // clamp and the reciprocal have no packed form.  p and a are [coordinate][pair of query points].  The values are those
 // of the scalar statements of the header: d^2 = fma(d_c, d_c, ...) over the coordinates in order, from d_0 d_0.
@@ -94,7 +50,7 @@ __device__ __forceinline__ void repulsion_run(const float *__restrict__ y, int j
 #pragma unroll 8
   for (int j = j0; j < j1; ++j) {                                    // j is workgroup-uniform: scalar loads, eight keys each
     float k[D];
-    load_point<D>(y, j, k);
+    load_point<D>(y, D, j, k);
 #pragma unroll
     for (int h = 0; h < kQ / 2; ++h) {
       float2v d[D], d2;
@@ -125,7 +81,7 @@ __global__ __launch_bounds__(256) void spring_repulsion_kernel(const float *__re
   for (int t = 0; t < kQ; ++t) {
     qi[t] = q0 + 256 * t + (int)threadIdx.x;
     float v[D];
-    load_point<D>(y, min(qi[t], N - 1), v);
+    load_point<D>(y, D, min(qi[t], N - 1), v);
 #pragma unroll
     for (int cc = 0; cc < D; ++cc) {
       p[cc][t / 2][t % 2] = v[cc];
@@ -161,20 +117,14 @@ __global__ __launch_bounds__(256) void spring_repulsion_fold_kernel(const double
   const int i = blockIdx.x * 256 + (int)threadIdx.x;
   if (i >= N) return;
   double s[D];
+  fold_chunks<D>(part, chunks, N, i, s);
 #pragma unroll
-  for (int cc = 0; cc < D; ++cc) s[cc] = 0.0;
-  for (int c = 0; c < chunks; ++c) {
-    const double *o = part + (int64_t)c * D * N;
-#pragma unroll
-    for (int cc = 0; cc < D; ++cc) s[cc] += o[(int64_t)cc * N + i];
-  }
-#pragma unroll
-  for (int cc = 0; cc < D; ++cc) rep[(int64_t)i * D + cc] = s[cc];
+  for (int c = 0; c < D; ++c) rep[(int64_t)i * D + c] = s[c];
 }
 
 template <int D>
 int launch_repulsion(const float *y, int64_t N, double *rep, const State *state, void *workspace, hipStream_t stream) {
-  const int chunk = chunk_keys(N), chunks = chunk_count(N);
+  const int chunk = nbody_chunk_keys(N, kChunk0), chunks = nbody_chunk_count(N, kChunk0);
   double *part = (double *)workspace;
   spring_repulsion_kernel<D><<<dim3((unsigned)((N + kTile - 1) / kTile), (unsigned)chunks), dim3(256), 0, stream>>>(
       y, (int)N, chunk, state, part);
@@ -187,8 +137,7 @@ int launch_repulsion(const float *y, int64_t N, double *rep, const State *state,
 struct StepArgs {
   const float *y;
   float *y_out;
-  int64_t N, nnz;
-  const int64_t *indptr, *indices;
+  CsrRows rows;
   const float *val;
   const uint8_t *fixed;
   const double *rep;
@@ -199,103 +148,42 @@ struct StepArgs {
   double *rowsq;                     // [N]: the rows' sum of delta^2
 };
 
-__device__ __forceinline__ int64_t clamp_pos(int64_t p, int64_t n) { return p < 0 ? 0 : (p > n ? n : p); }
+// entry e of the row at yi: max(|d|, 0.01) w d
+struct SpringEntry {
+  const StepArgs &A;
 
-// the largest row r with indptr[r] <= p: the row that holds entry p
-__device__ __forceinline__ int64_t row_of(const StepArgs &A, int64_t p) {
-  int64_t lo = 0, hi = A.N - 1;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (A.indptr[mid] <= p) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-// where the sum of group g of a row that starts at entry `beg` lies: rows r' < r hold at most beg / 64 + r groups
-__device__ __forceinline__ int64_t group_slot(int64_t beg, int64_t r, int64_t g) { return beg / kGroup + r + g; }
-
-// the group of 64 entries at g0 of a row at yi that ends at `end`: every lane returns the sums
-template <int D>
-__device__ __forceinline__ void group_sum(const StepArgs &A, const float (&yi)[D], int64_t g0, int64_t end, int lane,
-                                          float (&s)[D]) {
-#pragma unroll
-  for (int c = 0; c < D; ++c) s[c] = 0.f;
-  const int64_t e = g0 + lane;
-  if (e < end) {
-    int64_t j = A.indices[e];
-    j = j < 0 ? 0 : (j >= A.N ? A.N - 1 : j);                        // clamped, never followed out of the array
+  template <int D>
+  __device__ __forceinline__ void operator()(const float (&yi)[D], int64_t e, float (&s)[D]) const {
     float yj[D], d[D];
-    load_point<D>(A.y, j, yj);
+    load_point<D>(A.y, D, A.rows.col(e), yj);
     const float dist = fmaxf(__fsqrt_rn(difference<D>(yi, yj, d)), kMinDist);
     const float w = A.val ? A.val[e] * dist : dist;
 #pragma unroll
     for (int c = 0; c < D; ++c) s[c] = fmaf(w, d[c], s[c]);
   }
-#pragma unroll
-  for (int c = 0; c < D; ++c) s[c] = wave_sum(s[c]);
-}
+};
 
 template <int D>
 __global__ __launch_bounds__(256) void spring_parts_kernel(const StepArgs A) {
   if (A.state->done) return;                                         // grid-uniform
-  const int lane = threadIdx.x & 63;
-  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t p0 = w * A.part;
-  if (p0 >= A.nnz) return;                                           // wave-uniform
-  const int64_t pl = min(p0 + A.part, A.nnz) - 1;
-  const int64_t ra = row_of(A, p0), rb = row_of(A, pl);
-  for (int side = 0; side < 2; ++side) {
-    if (side == 1 && rb == ra) break;
-    const int64_t r = side ? rb : ra;
-    const int64_t beg = clamp_pos(A.indptr[r], A.nnz), end = clamp_pos(A.indptr[r + 1], A.nnz);
-    if (end - beg <= A.part) continue;
-    int64_t ps = beg;                                                // side 1: the row starts inside the window
-    if (side == 0) {
-      ps = beg + (p0 - beg + A.part - 1) / A.part * A.part;          // the first part of row ra that starts at or after p0
-      if (ps > pl || ps >= end || ps < p0) continue;
-    } else if (beg <= p0 || beg > pl) {
-      continue;
-    }
-    float yi[D], s[D];
-    load_point<D>(A.y, r, yi);
-    const int64_t pe = min(ps + A.part, end);
-    for (int64_t g0 = ps; g0 < pe; g0 += kGroup) {
-      group_sum<D>(A, yi, g0, pe, lane, s);
-      float *o = A.groups + group_slot(beg, r, (g0 - beg) / kGroup) * D;
-#pragma unroll
-      for (int c = 0; c < D; ++c)
-        if (lane == c) o[c] = s[c];
-    }
-  }
+  gather_parts<D>(A.rows, A.y, D, A.part, A.groups, SpringEntry{A});
 }
 
 template <int D>
 __global__ __launch_bounds__(256) void spring_step_kernel(const StepArgs A) {
   const int lane = threadIdx.x & 63;
   const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= A.N) return;                                              // wave-uniform
+  if (i >= A.rows.N) return;                                         // wave-uniform
   float yi[D];
-  load_point<D>(A.y, i, yi);
+  load_point<D>(A.y, D, i, yi);
   if (A.state->done) {                                               // grid-uniform: the latch
     if (lane < D) A.y_out[i * D + lane] = A.y[i * D + lane];
     return;
   }
-  const int64_t beg = clamp_pos(A.indptr[i], A.nnz), end = max(beg, clamp_pos(A.indptr[i + 1], A.nnz));
+  const double acc = gather_row<D>(A.rows, A.y, D, A.part, A.groups, i, lane, SpringEntry{A});    // lane c: coordinate c
   double att[D];
 #pragma unroll
-  for (int c = 0; c < D; ++c) att[c] = 0.0;
-  if (end - beg <= A.part) {
-    float s[D];
-    for (int64_t g0 = beg; g0 < end; g0 += kGroup) {
-      group_sum<D>(A, yi, g0, end, lane, s);
-#pragma unroll
-      for (int c = 0; c < D; ++c) att[c] += (double)s[c];
-    }
-  } else if (lane == 0) {
-    const float *o = A.groups + group_slot(beg, i, 0) * D;
-    for (int64_t g = 0, n = (end - beg + kGroup - 1) / kGroup; g < n; ++g)
-#pragma unroll
-      for (int c = 0; c < D; ++c) att[c] += (double)o[g * D + c];
-  }
+  for (int c = 0; c < D; ++c) att[c] = __shfl(acc, c, 64);
   if (lane != 0) return;
   const double t = A.state->t, k2 = A.k * A.k;
   double disp[D], l2 = 0.0;
@@ -325,37 +213,28 @@ __global__ __launch_bounds__(256) void spring_finish_kernel(const double *__rest
   if (state->done) return;                                           // every lane reads it before lane 0 writes (below the tree)
   double v = 0.0;
   for (int64_t i = threadIdx.x; i < N; i += 256) v += rowsq[i];
-  s[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
-    __syncthreads();
-  }
+  v = block_sum_f64(v, s);
   if (threadIdx.x == 0) {
     state->t -= state->dt;
     state->ran += 1;
-    state->done = sqrt(s[0]) / (double)N < threshold ? 1 : 0;
+    state->done = sqrt(v) / (double)N < threshold ? 1 : 0;
   }
 }
 
 template <int D>
 int launch_step(const StepArgs &A, hipStream_t stream) {
-  if (A.nnz > A.part) {                                              // no row is longer than a part otherwise
-    const int64_t windows = (A.nnz + A.part - 1) / A.part;
+  if (A.rows.nnz > A.part) {                                         // no row is longer than a part otherwise
+    const int64_t windows = window_count(A.rows.nnz, A.part);
     spring_parts_kernel<D><<<dim3((unsigned)((windows + 3) / 4)), dim3(256), 0, stream>>>(A);
     if (int rc = ampconv_launch_status()) return rc;
   }
-  spring_step_kernel<D><<<dim3((unsigned)((A.N + 3) / 4)), dim3(256), 0, stream>>>(A);
+  spring_step_kernel<D><<<dim3((unsigned)((A.rows.N + 3) / 4)), dim3(256), 0, stream>>>(A);
   if (int rc = ampconv_launch_status()) return rc;
-  spring_finish_kernel<<<dim3(1), dim3(256), 0, stream>>>(A.rowsq, A.N, A.threshold, A.state);
+  spring_finish_kernel<<<dim3(1), dim3(256), 0, stream>>>(A.rowsq, A.rows.N, A.threshold, A.state);
   return ampconv_launch_status();
 }
 
-bool aligned8(const void *p) { return p && (uintptr_t)p % 8 == 0; }
-bool aligned4(const void *p) { return p && (uintptr_t)p % 4 == 0; }
 bool shape_ok(int64_t N, int dim) { return N >= 1 && N <= AMPCONV_SPRING_MAX_N && (dim == 2 || dim == 3); }
-size_t groups_bytes(int64_t N, int64_t nnz, int dim) { return pad256((size_t)(nnz / kGroup + N + 1) * (size_t)dim * sizeof(float)); }
 
 }  // namespace
 
@@ -368,7 +247,7 @@ extern "C" int ampconv_spring_start(float *y, int64_t N, int dim, uint64_t seed,
 
 extern "C" size_t ampconv_spring_repulsion_workspace_bytes(int64_t N, int dim) {
   if (!shape_ok(N, dim)) return 0;
-  return pad256((size_t)chunk_count(N) * (size_t)dim * (size_t)N * sizeof(double));
+  return pad256((size_t)nbody_chunk_count(N, kChunk0) * (size_t)dim * (size_t)N * sizeof(double));
 }
 
 extern "C" int ampconv_spring_repulsion(const float *y, int64_t N, int dim, double *rep, const ampconv_spring_state *state,
@@ -397,7 +276,7 @@ extern "C" int ampconv_spring_step_split(const float *y_in, float *y_out, int64_
   if (!workspace || (uintptr_t)workspace % 8 || workspace_bytes < ampconv_spring_step_workspace_bytes(N, nnz, dim))
     return AMPCONV_E_WORKSPACE;
   StepArgs A = {};
-  A.y = y_in; A.y_out = y_out; A.N = N; A.nnz = nnz; A.indptr = indptr; A.indices = indices; A.val = val; A.fixed = fixed;
+  A.y = y_in; A.y_out = y_out; A.rows = {indptr, indices, N, nnz}; A.val = val; A.fixed = fixed;
   A.rep = rep; A.k = k; A.threshold = threshold; A.state = state; A.part = part;
   A.groups = (float *)workspace;
   A.rowsq = (double *)((char *)workspace + groups_bytes(N, nnz, dim));

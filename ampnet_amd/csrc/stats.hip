@@ -109,12 +109,7 @@ __device__ __forceinline__ uint32_t load_chunk(const ampconv_stats_tensor_t &d, 
                                  : load_chunk((const uint32_t *)d.x, d.numel, c, aligned, u);
 }
 
-// ---- wave butterflies (every lane ends with the result)
-__device__ __forceinline__ double wave_sum_f64(double x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
+// ---- wave butterflies (every lane ends with the result; wave_sum_f64 is common.h's)
 __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t x) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) x += (uint64_t)__shfl_xor((unsigned long long)x, o, 64);

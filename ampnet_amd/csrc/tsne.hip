@@ -7,24 +7,16 @@
 // the search is scikit-learn's _binary_search_perplexity statement by statement in fp64, the two sums per step by a
 // butterfly (every lane ends with the same bits, so the branch is wave-uniform).
 //
-// Repulsion.  A VALU N-body kernel: the inner dimension is 2, the matrix cores have nothing to offer.  A workgroup
-// of 256 lanes owns AMPCONV_TSNE_TILE = 1024 query points (four per lane: four independent reciprocals in flight,
-// a key is read once for four pairs) and one chunk of keys.  Keys are read at a wave-uniform address (one scalar
-// load serves the wave: the broadcast costs no LDS and no vector memory traffic) and enter the VALU as scalar
-// operands.  Per pair: two subtractions, two FMAs for 1 + d^2, v_rcp_f32, one addition, one product, two FMAs.
-// The fp32 sums live for a run of AMPCONV_TSNE_RUN keys, in key order, then go into fp64 registers; a chunk's fp64
-// sums go to the workspace [chunk][3][N] and tsne_repulsion_fold_kernel adds the chunks in order.  The chunk length is a
-// function of N alone, so the bits do not depend on how the work is spread.  j = i is excluded by index, in the one
-// chunk that holds the workgroup's own points (a workgroup-uniform choice of loop); everywhere else the loop has no
-// compare.  Z: per row in fp64, 256 rows by a fixed tree, the workgroups' sums by one workgroup in a fixed order.
+// Repulsion.  The chunked N-body pass of layout_common.h with three planes: x, y and the row's share of Z.  Per pair:
+// two subtractions, two FMAs for 1 + d^2, v_rcp_f32, one addition, one product, two FMAs.  j = i is excluded by index, in
+// the one chunk that holds the workgroup's own points (a workgroup-uniform choice of loop); everywhere else the loop has
+// no compare.  Z: per row in fp64, 256 rows by a fixed tree, the workgroups' sums by one workgroup in a fixed order.
 //
-// Step.  One wave per row of the CSR of P: lane l takes the entries l, l + 64, ... of the row in fp32, a butterfly adds
-// the lanes.  A row longer than AMPCONV_TSNE_PART entries is cut into parts of that length, counted from the row's
-// start; tsne_parts_kernel sums them (one wave per window of PART positions of the entry array: at most two parts start
-// in a window -- one of the row that holds the window's first position, one of a long row that starts inside it -- so
-// no plan and no read-back is needed) and the row's wave adds its parts in order in fp64.  The lane-0 tail is
-// scikit-learn's _gradient_descent for the row's two coordinates.
-#include "common.h"
+// Step.  One wave per row of the CSR of P with layout_common.h's long-row scheme at AMPCONV_TSNE_PART: lane l takes the
+// entries l, l + 64, ... of a row or a part in fp32 (part_sum), tsne_parts_kernel stores the sums of the parts that start
+// in a window as [2 sides][4], and the row's wave adds its parts in order in fp64.  The lane-0 tail is scikit-learn's
+// _gradient_descent for the row's two coordinates.
+#include "layout_common.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -38,16 +30,7 @@ constexpr int kTile = AMPCONV_TSNE_TILE;
 constexpr int kChunk0 = AMPCONV_TSNE_CHUNK;
 constexpr int kPart = AMPCONV_TSNE_PART;
 constexpr int kQ = kTile / 256;              // query points per lane
-constexpr int kMaxChunks = 64;
 static_assert(kMaxK == 256 && kChunk0 % kRun == 0 && kTile % 256 == 0, "lane maps of this file");
-
-inline size_t pad256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-__device__ __forceinline__ double wave_sum_f64(double x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
 
 // ------------------------------------------------------------------------------------------------------ affinities
 __global__ __launch_bounds__(256) void tsne_affinity_kernel(const float *__restrict__ dist2, int64_t N, int K, int64_t ldd,
@@ -104,13 +87,6 @@ __global__ __launch_bounds__(256) void tsne_affinity_kernel(const float *__restr
 }
 
 // ------------------------------------------------------------------------------------------------------- repulsion
-// keys per chunk, from N alone: AMPCONV_TSNE_CHUNK times ceil(ceil(N / AMPCONV_TSNE_CHUNK) / 64), so at most 64 chunks
-int chunk_keys(int64_t N) {
-  const int64_t c0 = (N + kChunk0 - 1) / kChunk0;
-  return kChunk0 * (int)((c0 + kMaxChunks - 1) / kMaxChunks);
-}
-int chunk_count(int64_t N) { return (int)((N + chunk_keys(N) - 1) / chunk_keys(N)); }
-
 template <bool SELF>
 __device__ __forceinline__ void repulsion_run(const float2 *__restrict__ y, int j0, int j1, const float (&xi)[kQ],
                                               const float (&yi)[kQ], const int (&qi)[kQ], float (&ax)[kQ], float (&ay)[kQ],
@@ -168,50 +144,24 @@ __global__ __launch_bounds__(256) void tsne_repulsion_kernel(const float2 *__res
     }
 }
 
-// the tree of a 256-lane workgroup, one fixed order
-__device__ __forceinline__ double block_tree_sum(double v, double *s) {
-  s[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
-    __syncthreads();
-  }
-  return s[0];
-}
-
 __global__ __launch_bounds__(256) void tsne_repulsion_fold_kernel(const double *__restrict__ part, int chunks, int N,
                                                                   float2 *__restrict__ neg_f, double *__restrict__ zpart) {
   __shared__ double s[256];
   const int i = blockIdx.x * 256 + (int)threadIdx.x;
-  double sx = 0.0, sy = 0.0, sq = 0.0;
+  double f[3] = {0.0, 0.0, 0.0};
   if (i < N) {
-    for (int c = 0; c < chunks; ++c) {
-      const double *o = part + (int64_t)c * 3 * N;
-      sx += o[i]; sy += o[(int64_t)N + i]; sq += o[2 * (int64_t)N + i];
-    }
-    neg_f[i] = make_float2((float)sx, (float)sy);
+    fold_chunks<3>(part, chunks, N, i, f);
+    neg_f[i] = make_float2((float)f[0], (float)f[1]);
   }
-  const double z = block_tree_sum(sq, s);
+  const double z = block_sum_f64(f[2], s);
   if (threadIdx.x == 0) zpart[blockIdx.x] = z;
-}
-
-// out[v] = the sum of in[v n .. v n + n): lane t adds the elements t, t + 256, ... in order, then the tree
-__global__ __launch_bounds__(256) void tsne_sum_kernel(const double *__restrict__ in, int64_t n, double *__restrict__ out) {
-  __shared__ double s[256];
-  const double *p = in + (int64_t)blockIdx.x * n;
-  double v = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += 256) v += p[i];
-  v = block_tree_sum(v, s);
-  if (threadIdx.x == 0) out[blockIdx.x] = v;
 }
 
 // ------------------------------------------------------------------------------------------------------------ step
 struct StepArgs {
   const float2 *y;
   float2 *y_out, *update, *gains;
-  int64_t N, nnz;
-  const int64_t *indptr, *indices;
+  CsrRows rows;
   const float *val;
   const float2 *neg;
   const double *Z;
@@ -221,26 +171,12 @@ struct StepArgs {
   double *rowerr;                    // [2][N]: the rows' error terms, the rows' squared gradient norms
 };
 
-__device__ __forceinline__ int64_t clamp_pos(int64_t p, int64_t n) { return p < 0 ? 0 : (p > n ? n : p); }
-
-// the largest row r with indptr[r] <= p: the row that holds entry p
-__device__ __forceinline__ int64_t row_of(const StepArgs &a, int64_t p) {
-  int64_t lo = 0, hi = a.N - 1;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (a.indptr[mid] <= p) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 // entries [b, e) of a row at yi, e - b <= AMPCONV_TSNE_PART, by one wave; every lane returns the sums
 __device__ __forceinline__ void part_sum(const StepArgs &a, float2 yi, int64_t b, int64_t e, double Z, int lane, float &sx,
                                          float &sy, float &kl) {
   sx = sy = kl = 0.f;
   for (int64_t p = b + lane; p < e; p += 64) {
-    int64_t j = a.indices[p];
-    j = j < 0 ? 0 : (j >= a.N ? a.N - 1 : j);                        // clamped, never followed out of the array
-    const float2 yj = a.y[j];
+    const float2 yj = a.y[a.rows.col(p)];
     const float pv = a.exag * a.val[p];
     const float dx = yi.x - yj.x, dy = yi.y - yj.y;
     const float q = __builtin_amdgcn_rcpf(fmaf(dx, dx, fmaf(dy, dy, 1.f)));
@@ -258,37 +194,23 @@ __device__ __forceinline__ void part_sum(const StepArgs &a, float2 yi, int64_t b
 __global__ __launch_bounds__(256) void tsne_parts_kernel(const StepArgs a) {
   const int lane = threadIdx.x & 63;
   const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t p0 = w * kPart;
-  if (p0 >= a.nnz) return;                                           // wave-uniform
-  const int64_t pl = min(p0 + kPart, a.nnz) - 1;
-  const int64_t ra = row_of(a, p0), rb = row_of(a, pl);
   const double Z = fmax(*a.Z, DBL_EPSILON);
-  for (int s = 0; s < 2; ++s) {
-    if (s == 1 && rb == ra) break;
-    const int64_t r = s ? rb : ra;
-    const int64_t beg = clamp_pos(a.indptr[r], a.nnz), end = clamp_pos(a.indptr[r + 1], a.nnz);
-    if (end - beg <= kPart) continue;
-    int64_t ps = beg;                                                // s = 1: the row starts inside the window
-    if (s == 0) {
-      ps = beg + (p0 - beg + kPart - 1) / kPart * kPart;             // the first part of row ra that starts at or after p0
-      if (ps > pl || ps >= end || ps < p0) continue;
-    } else if (beg <= p0 || beg > pl) {
-      continue;
-    }
+  for_window_parts(a.rows, kPart, w, [&](int64_t r, int64_t, int64_t, int64_t ps, int64_t pe, int side) {
     float sx, sy, kl;
-    part_sum(a, a.y[r], ps, min(ps + kPart, end), Z, lane, sx, sy, kl);
+    part_sum(a, a.y[r], ps, pe, Z, lane, sx, sy, kl);
     if (lane == 0) {
-      float *o = a.parts + (2 * w + s) * 4;
+      float *o = a.parts + (2 * w + side) * 4;
       o[0] = sx; o[1] = sy; o[2] = kl;
     }
-  }
+  });
 }
 
 __global__ __launch_bounds__(256) void tsne_step_kernel(const StepArgs a) {
   const int lane = threadIdx.x & 63;
   const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= a.N) return;                                              // wave-uniform
-  const int64_t beg = clamp_pos(a.indptr[i], a.nnz), end = max(beg, clamp_pos(a.indptr[i + 1], a.nnz));
+  if (i >= a.rows.N) return;                                         // wave-uniform
+  int64_t beg, end;
+  a.rows.span(i, beg, end);
   const float2 yi = a.y[i];
   const double Z = fmax(*a.Z, DBL_EPSILON);
   double px, py, pk;
@@ -325,12 +247,11 @@ __global__ __launch_bounds__(256) void tsne_step_kernel(const StepArgs a) {
   a.y_out[i] = make_float2(yo[0], yo[1]);
   if (a.err) {
     a.rowerr[i] = pk;
-    a.rowerr[a.N + i] = (double)gg[0] * (double)gg[0] + (double)gg[1] * (double)gg[1];
+    a.rowerr[a.rows.N + i] = (double)gg[0] * (double)gg[0] + (double)gg[1] * (double)gg[1];
   }
 }
 
-bool aligned8(const void *p) { return p && (uintptr_t)p % 8 == 0; }
-int64_t windows(int64_t nnz) { return (nnz + kPart - 1) / kPart; }
+int64_t windows(int64_t nnz) { return window_count(nnz, kPart); }
 
 }  // namespace
 
@@ -346,7 +267,7 @@ extern "C" int ampconv_tsne_affinities(const float *dist2, int64_t N, int K, int
 
 extern "C" size_t ampconv_tsne_repulsion_workspace_bytes(int64_t N) {
   if (N < 1 || N > AMPCONV_TSNE_MAX_N) return 0;
-  return pad256((size_t)chunk_count(N) * 3 * (size_t)N * sizeof(double)) + pad256((size_t)((N + 255) / 256) * sizeof(double));
+  return pad256((size_t)nbody_chunk_count(N, kChunk0) * 3 * (size_t)N * sizeof(double)) + pad256((size_t)((N + 255) / 256) * sizeof(double));
 }
 
 extern "C" int ampconv_tsne_repulsion(const float *y, int64_t N, float *neg_f, double *Z, void *workspace,
@@ -355,7 +276,7 @@ extern "C" int ampconv_tsne_repulsion(const float *y, int64_t N, float *neg_f, d
   if (!aligned8(y) || !aligned8(neg_f) || !aligned8(Z) || N < 1 || N > AMPCONV_TSNE_MAX_N) return AMPCONV_E_BADARG;
   if (!workspace || (uintptr_t)workspace % 8 || workspace_bytes < ampconv_tsne_repulsion_workspace_bytes(N))
     return AMPCONV_E_WORKSPACE;
-  const int chunk = chunk_keys(N), chunks = chunk_count(N);
+  const int chunk = nbody_chunk_keys(N, kChunk0), chunks = nbody_chunk_count(N, kChunk0);
   const int blocks = (int)((N + 255) / 256);
   double *part = (double *)workspace;
   double *zpart = (double *)((char *)workspace + pad256((size_t)chunks * 3 * (size_t)N * sizeof(double)));
@@ -364,7 +285,7 @@ extern "C" int ampconv_tsne_repulsion(const float *y, int64_t N, float *neg_f, d
   if (int rc = ampconv_launch_status()) return rc;
   tsne_repulsion_fold_kernel<<<dim3((unsigned)blocks), dim3(256), 0, stream>>>(part, chunks, (int)N, (float2 *)neg_f, zpart);
   if (int rc = ampconv_launch_status()) return rc;
-  tsne_sum_kernel<<<dim3(1), dim3(256), 0, stream>>>(zpart, blocks, Z);
+  sum_rows_kernel<<<dim3(1), dim3(256), 0, stream>>>(zpart, blocks, Z);
   return ampconv_launch_status();
 }
 
@@ -387,7 +308,7 @@ extern "C" int ampconv_tsne_step(const float *y_in, float *y_out, float *update,
     return AMPCONV_E_WORKSPACE;
   StepArgs a = {};
   a.y = (const float2 *)y_in; a.y_out = (float2 *)y_out; a.update = (float2 *)update; a.gains = (float2 *)gains;
-  a.N = N; a.nnz = nnz; a.indptr = indptr; a.indices = indices; a.val = val;
+  a.rows = {indptr, indices, N, nnz}; a.val = val;
   a.neg = (const float2 *)neg_f; a.Z = Z;
   a.exag = exaggeration; a.mom = momentum; a.lr = learning_rate; a.min_gain = min_gain;
   a.err = error != nullptr;
@@ -400,7 +321,7 @@ extern "C" int ampconv_tsne_step(const float *y_in, float *y_out, float *update,
   tsne_step_kernel<<<dim3((unsigned)((N + 3) / 4)), dim3(256), 0, stream>>>(a);
   if (int rc = ampconv_launch_status()) return rc;
   if (error) {
-    tsne_sum_kernel<<<dim3(2), dim3(256), 0, stream>>>(a.rowerr, N, error);
+    sum_rows_kernel<<<dim3(2), dim3(256), 0, stream>>>(a.rowerr, N, error);
     return ampconv_launch_status();
   }
   return AMPCONV_OK;
