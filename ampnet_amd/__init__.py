@@ -26,6 +26,8 @@ from .pca import PCAResult, pca
 from .tsne import TSNEResult, neighbor_preservation, tsne
 from .umap import UMAPResult, umap
 from .spring import SpringLayout, SpringResult, spring_layout
+from .random_graphs import (BlockModelGraph, XorLinkData, gnp_random_graph, random_partition_graph, stochastic_block_model,
+                            xor_link_dataset)
 
 __all__ = ['AMPConv', 'InvalidConfiguration', 'EdgeCSR', 'graph_cache', 'distributed', 'AMPGCN', 'FeatureTokens',
            'GraphSAINTRandomWalkSampler', 'NodePartition', 'PartitionedAMPConv', 'GraphedAMPConv', 'AttentionHeatmap', 'top_features',
@@ -34,4 +36,6 @@ __all__ = ['AMPConv', 'InvalidConfiguration', 'EdgeCSR', 'graph_cache', 'distrib
            'TensorStats', 'tensor_stats', 'GCNConv', 'GCN', 'gcn_norm', 'gcn_aggregate', 'gcn_input_linear',
            'pair_loss', 'PairLoss', 'walk_pairs', 'knn', 'knn_graph', 'knn_classify', 'pca', 'PCAResult',
            'tsne', 'TSNEResult', 'neighbor_preservation', 'umap', 'UMAPResult',
-           'spring_layout', 'SpringResult', 'SpringLayout']
+           'spring_layout', 'SpringResult', 'SpringLayout',
+           'stochastic_block_model', 'random_partition_graph', 'gnp_random_graph', 'xor_link_dataset', 'BlockModelGraph',
+           'XorLinkData']

@@ -79,6 +79,7 @@ STATS_RECORD_BYTES = 88   # sizeof(ampconv_stats_record_t)
 PCA_RUN, PCA_MAX_W, PCA_MAX_K = 32, 2048, 128    # AMPCONV_PCA_RUN (rows summed in fp32 before the fp64 fold), _MAX_W, _MAX_K
 TSNE_MAX_K, TSNE_MAX_N, TSNE_RUN, TSNE_TILE, TSNE_CHUNK, TSNE_PART = 256, 1 << 24, 256, 1024, 4096, 1024    # AMPCONV_TSNE_*
 UMAP_MAX_K, UMAP_MAX_M, UMAP_MAX_DIM, UMAP_PART = 256, 1 << 24, 32, 1024      # AMPCONV_UMAP_*
+SBM_MAX_K = 256          # AMPCONV_SBM_MAX_K: blocks of a stochastic block model
 SPRING_MAX_N, SPRING_RUN, SPRING_TILE, SPRING_CHUNK, SPRING_PART = 1 << 24, 256, 1024, 4096, 1024      # AMPCONV_SPRING_*
 GCN_LONG_SEGMENT = 256   # AMPCONV_GCN_LONG_SEGMENT: a CSR/CSC segment from this length on is summed by whole workgroups
 
@@ -240,6 +241,8 @@ SIGNATURES = {
                                    _vp, _sz, _vp]),
     'ampconv_spring_step_split': (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, ctypes.c_double, ctypes.c_double,
                                          _vp, _i32, _vp, _sz, _vp]),
+    'ampconv_sbm_count': (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, ctypes.c_uint64, _vp, _vp, _vp]),
+    'ampconv_sbm_fill': (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, ctypes.c_uint64, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None

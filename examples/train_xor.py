@@ -5,6 +5,11 @@ scikit-learn's NearestNeighbors, an [N, N] adjacency matrix and two Python loops
 xor_training_utils.py:58-72 trained full-batch.
 
     python examples/train_xor.py [--nodes 400] [--neighbours 10] [--noise 0.1] [--epochs 200]
+    python examples/train_xor.py --graph links [--same-prob 0.7] [--diff-prob 0.1]
+
+--graph links: the reference's other XOR data, create_xor_data (:104-165) -- every ordered pair of nodes linked with
+same_class_link_prob or diff_class_link_prob -- drawn on the device by ampnet_amd.xor_link_dataset in place of its
+loops over an [N, N] matrix.
 
 feature_repeats is 1, the value the reference's factory works with: it sets num_node_features = 2 feature_repeats next to
 num_sampled_vectors = 2, which its full-width token branch takes only when the two agree.
@@ -20,7 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
-from ampnet_amd import AMPGCN, knn_graph  # noqa: E402
+from ampnet_amd import AMPGCN, knn_graph, xor_link_dataset  # noqa: E402
 
 FEATURE_REPEATS = 1
 
@@ -36,20 +41,33 @@ def duplicated_xor(n, noise_std, k, device, gen):
     return types.SimpleNamespace(x=x, y=y, edge_index=knn_graph(x, k), num_nodes=n)
 
 
+def xor_links(n, noise_std, same_prob, diff_prob, device, seed):
+    """create_xor_data's x, y and directed link graph (feature_repeats 1), y as class indices."""
+    d = xor_link_dataset(n, noise_std, same_prob, diff_prob, seed=seed, device=device)
+    return types.SimpleNamespace(x=d.x, y=d.y.long(), edge_index=d.edge_index, num_nodes=n)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--nodes', type=int, default=400)
     ap.add_argument('--neighbours', type=int, default=10)
     ap.add_argument('--noise', type=float, default=0.1)
     ap.add_argument('--epochs', type=int, default=200)
+    ap.add_argument('--graph', choices=('knn', 'links'), default='knn')
+    ap.add_argument('--same-prob', type=float, default=0.7, help='--graph links: same_class_link_prob')
+    ap.add_argument('--diff-prob', type=float, default=0.1, help='--graph links: diff_class_link_prob')
     args = ap.parse_args(argv)
     device = torch.device('cuda:0')
     torch.manual_seed(0)
     gen = torch.Generator(device=device).manual_seed(0)
     torch.cuda.synchronize()
     t0 = time.time()
-    train = duplicated_xor(args.nodes, args.noise, args.neighbours, device, gen)
-    test = duplicated_xor(args.nodes, args.noise, args.neighbours, device, gen)
+    if args.graph == 'links':
+        train = xor_links(args.nodes, args.noise, args.same_prob, args.diff_prob, device, seed=0)
+        test = xor_links(args.nodes, args.noise, args.same_prob, args.diff_prob, device, seed=1)
+    else:
+        train = duplicated_xor(args.nodes, args.noise, args.neighbours, device, gen)
+        test = duplicated_xor(args.nodes, args.noise, args.neighbours, device, gen)
     torch.cuda.synchronize()
     print(f'two graphs of {args.nodes} nodes x {train.edge_index.size(1)} edges built on the device in '
           f'{1e3 * (time.time() - t0):.1f} ms (first call: library load included)')

@@ -1407,6 +1407,57 @@ int ampconv_spring_step_split(const float *y_in, float *y_out, int64_t N, int di
                               double k, double threshold, ampconv_spring_state *state, int part, void *workspace,
                               size_t workspace_bytes, void *stream);
 
+/* ---- stochastic block model graphs (csrc/sbm.hip; pure additions, the ABI number stays 111) -------------------------
+ * Random graphs with class structure, drawn on the device: ampnet_amd.random_graphs (stochastic_block_model,
+ * random_partition_graph, gnp_random_graph, xor_link_dataset -- the link data of the reference's
+ * synthetic_benchmark/synthetic_xor.py:104-165 and the graph of synthetic_rpg.py:39-121).
+ *
+ * THE BLOCK MODEL (a contract, like THE WALK STREAM: tests rebuild it on the host, tests/sbm_reference.py).
+ *   inputs: sizes[K], every entry >= 0, N = sum(sizes); start[0] = 0, start[b + 1] = start[b] + sizes[b]; block b is the
+ *   contiguous node range [start[b], start[b + 1]), block(u) the block that holds node u.  P fp64 [K, K] row-major,
+ *   every entry in [0, 1].  Flags `directed` and `selfloops`, a 64-bit seed.
+ *   unit (u, b), u a node and b a block: its candidates C(u, b) are the nodes v of block b in ascending order, without
+ *   v == u unless `selfloops`, and, if not `directed`, only those with v > u (v >= u with `selfloops`).  m = |C|,
+ *   p = P[block(u)][b].  m == 0 or p <= 0: no edge.  p >= 1: every candidate.  Otherwise, with
+ *     lq = log1p(-p)       taken on the HOST in fp64 (numpy.log1p) and handed to the calls as the [K, K] table `lq`, so
+ *                          that a host model and the kernel share its bits,
+ *     draw(seed, a, b) = splitmix64(seed ^ splitmix64(a * 0x100000001B3 + b))      (uint64, wrapping: the library's stream)
+ *   start with j = -1 and for t = 0, 1, ...:
+ *     r = draw(seed, u K + b, t);  U = ((r >> 11) + 1) 2^-53, in (0, 1];  q = log(U) / lq in fp64;
+ *     if !(q < m - 1 - j): stop -- compared IN FP64, before any conversion to an integer (q reaches 1e300 for tiny p);
+ *     j += 1 + (int64)floor(q);  emit the edge (u, C[j]).
+ *   j grows by at least 1 per step and stays below m, so every chain ends.  The skips are geometric, hence memoryless:
+ *   every candidate pair is an independent Bernoulli(p) trial -- the distribution of networkx's
+ *   stochastic_block_model(sizes, p, directed=, selfloops=) and, up to the 2^-53 grid of U, of the reference's loops.
+ *   output, directed: the edges ordered by u, then b, then j: row-major (row, col) ascending, the order of the
+ *   reference's listing loops (synthetic_xor.py:158-162).  Undirected: that list of pairs u <= v, followed by the
+ *   mirrors (v, u) of its pairs with v != u in the same order.  edge_index int64 [2, E], block int64 [N].
+ *   limits: E <= 2^31 - 1, N <= 2^31 - 1, K <= AMPCONV_SBM_MAX_K.
+ * The only floating-point operation the device adds to the host's share is log(U) (the division is IEEE): a host model
+ * whose log is a few ulp from the device's gives the same graph unless some q lies that close to an integer.
+ *
+ * ampconv_sbm_count: count[u K + b] = the number of edges unit (u, b) emits (int64 [N K]); mcount (NULL: not wanted),
+ * the same shape: that number without the unit's self loop (u, u) -- the number of MIRRORS the unit has in an undirected
+ * graph.  Units with p >= 1 or p <= 0 are closed forms, the others walk their chain.
+ * ampconv_sbm_fill: walks the same chains and writes edge i of unit (u, b) to row[off[u K + b] + i] = u,
+ * col[...] = C[j]; off is the exclusive prefix sum of count (the caller's scan).  With moff (NULL: no mirrors) mirror i
+ * of the unit -- its edges with v != u, in order -- goes to position mirror_base + moff[u K + b] + i as (v, u); moff is the
+ * exclusive prefix sum of mcount (== off without self loops) and mirror_base the total of count.  E: the length of row
+ * and of col; a position outside [0, E) -- offsets that are not those of the same arguments -- is not written.
+ * Lane l of a wave takes node 64 w + l of ONE block b: the lanes share p (where they share block(u)) and nearly share
+ * m, and a wave lasts as long as its longest chain.  No atomics, every position written by exactly one lane: two calls
+ * give the same bits.  Nothing is allocated and nothing synchronised.
+ * sizes: a HOST array [K] (like the descriptors of ampconv_adam_step: it travels as a kernel argument); P, lq, count,
+ * mcount, off, moff, row, col: device pointers, 8-byte aligned.
+ * AMPCONV_E_BADARG (nothing launched): a NULL or misaligned pointer (mcount, moff may be NULL), K outside
+ * [1, AMPCONV_SBM_MAX_K], a negative size, N above 2^31 - 1, E or mirror_base negative.  N == 0 succeeds.  */
+#define AMPCONV_SBM_MAX_K 256
+int ampconv_sbm_count(const int64_t *sizes, int K, const double *P, const double *lq, int directed, int selfloops,
+                      uint64_t seed, int64_t *count, int64_t *mcount, void *stream);
+int ampconv_sbm_fill(const int64_t *sizes, int K, const double *P, const double *lq, int directed, int selfloops,
+                     uint64_t seed, const int64_t *off, const int64_t *moff, int64_t mirror_base, int64_t *row, int64_t *col,
+                     int64_t E, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
