@@ -82,6 +82,7 @@ UMAP_MAX_K, UMAP_MAX_M, UMAP_MAX_DIM, UMAP_PART = 256, 1 << 24, 32, 1024      # 
 SBM_MAX_K = 256          # AMPCONV_SBM_MAX_K: blocks of a stochastic block model
 SPRING_MAX_N, SPRING_RUN, SPRING_TILE, SPRING_CHUNK, SPRING_PART = 1 << 24, 256, 1024, 4096, 1024      # AMPCONV_SPRING_*
 GCN_LONG_SEGMENT = 256   # AMPCONV_GCN_LONG_SEGMENT: a CSR/CSC segment from this length on is summed by whole workgroups
+GCN_PART = 2048          # AMPCONV_GCN_PART: entries of a long segment that one workgroup sums
 
 # name -> (restype, argtypes); mirrors include/ampconv.h one to one
 SIGNATURES = {

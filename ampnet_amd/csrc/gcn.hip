@@ -461,7 +461,9 @@ extern "C" int ampconv_gcn_input_fwd(const float *x, int64_t N, int64_t F, const
                                      const float *W, const float *table, int De, int C, float *h, int64_t ld_h,
                                      void *workspace, size_t workspace_bytes, void *stream) {
   if (!input_args_ok(x, N, F, mean, inv_std, W, table, De, C) || !h || ld_h < C) return AMPCONV_E_BADARG;
-  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < input_fwd_bytes(F, C)) return AMPCONV_E_WORKSPACE;
+  // the size the header names covers both directions: held to it here too, though the forward uses less of it
+  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < ampconv_gcn_input_workspace_bytes(N, F, C))
+    return AMPCONV_E_WORKSPACE;
   if (N == 0) return AMPCONV_OK;
   if ((N + kRows - 1) / kRows > INT32_MAX) return AMPCONV_E_BADARG;
   hipStream_t st = (hipStream_t)stream;

@@ -46,6 +46,11 @@ def aggregate_backward(g, edge_index, improved=False, add_self_loops=True):
     return dh, g.sum(axis=0)
 
 
+def colsum(g):
+    """out[c] = sum_n g[n, c]."""
+    return np.asarray(g, dtype=np.float64).sum(axis=0)
+
+
 def dense_operator(edge_index, num_nodes, improved=False, add_self_loops=True):
     """A_hat [N, N] with out = A_hat h."""
     src, dst, norm, _ = gcn_norm(edge_index, num_nodes, improved, add_self_loops)
@@ -72,14 +77,22 @@ def embedded_input(z, table):
     return tokens.reshape(N, F * (table.shape[1] + 1))
 
 
-def first_layer_input(x, table, mode):
-    z = np.asarray(x, dtype=np.float64) if mode == 'raw' else zscore(x)
+def first_layer_input(x, table, mode, stats=None):
+    """stats: (mean, inv_std) to use as they are, z = (x - mean) inv_std, in place of zscore's own (a test of the input
+    kernels alone hands both sides the same fp32 statistics)."""
+    x = np.asarray(x, dtype=np.float64)
+    if mode == 'raw':
+        z = x
+    elif stats is None:
+        z = zscore(x)
+    else:
+        z = (x - np.asarray(stats[0], dtype=np.float64)) * np.asarray(stats[1], dtype=np.float64)
     return embedded_input(z, table) if mode == 'embedded' else z
 
 
-def input_linear(x, W, table, mode='embedded'):
+def input_linear(x, W, table, mode='embedded', stats=None):
     """h = X0 W^T on the materialised input X0."""
-    return first_layer_input(x, table, mode) @ np.asarray(W, dtype=np.float64).T
+    return first_layer_input(x, table, mode, stats) @ np.asarray(W, dtype=np.float64).T
 
 
 def input_linear_factored(x, W, table):
@@ -90,9 +103,9 @@ def input_linear_factored(x, W, table):
     return z @ W3[:, :, De].T + np.einsum('fk,jfk->j', table, W3[:, :, :De])
 
 
-def input_linear_backward(x, W, table, g, mode='embedded'):
+def input_linear_backward(x, W, table, g, mode='embedded', stats=None):
     """(dW, dtable) through the materialised input (dtable None outside the embedded mode)."""
-    X0, g = first_layer_input(x, table, mode), np.asarray(g, dtype=np.float64)
+    X0, g = first_layer_input(x, table, mode, stats), np.asarray(g, dtype=np.float64)
     dW = g.T @ X0
     if mode != 'embedded':
         return dW, None

@@ -4,6 +4,8 @@ tests/gcn_reference.py.  All inputs are CPU-seeded; references are computed once
 Tolerances: the project's flat bar (atol 1e-5, rtol 1e-4) on per-row outputs (out, dh, h, log-probabilities, the loss);
 parameter gradients (sums over the nodes) on the magnitude-scaled bar of conftest.assert_close_scaled.  With h, g ~ N(0, 1)
 a plain fp32 index_add_ restatement sits at <= 4.6e-6 on the ladder graph (hub of 2500, C = 64): the flat bar has room.
+What these shapes do not reach (C > 16 in the input kernels, more than 64 rows per chunk of the weight gradient, the
+column sum past 32768 rows, parts and long rows beyond one launch) is on the ladders of tests/test_gpu_gcn_kernels.py.
 """
 import functools
 import importlib.util
