@@ -16,6 +16,7 @@ from .graphed import GraphedAMPConv
 from .heatmap import AttentionHeatmap, top_features
 from .glue import ActDropout, TokenReadout, act_dropout, act_dropout_pool
 from .head import HeadMetrics, classifier_head, saint_nll_loss
+from .masked import MaskedMetrics, MaskedValueHead, build_masked_tokens, masked_value_loss
 from .norm import NormTokenReadout, TokenLayerNorm, norm_act_dropout, norm_act_dropout_pool
 from .optim import FusedAdam
 from .stats import TensorStats, tensor_stats
@@ -38,4 +39,4 @@ __all__ = ['AMPConv', 'InvalidConfiguration', 'EdgeCSR', 'graph_cache', 'distrib
            'tsne', 'TSNEResult', 'neighbor_preservation', 'umap', 'UMAPResult',
            'spring_layout', 'SpringResult', 'SpringLayout',
            'stochastic_block_model', 'random_partition_graph', 'gnp_random_graph', 'xor_link_dataset', 'BlockModelGraph',
-           'XorLinkData']
+           'XorLinkData', 'masked_value_loss', 'MaskedValueHead', 'MaskedMetrics', 'build_masked_tokens']

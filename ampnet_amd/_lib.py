@@ -244,6 +244,12 @@ SIGNATURES = {
                                          _vp, _i32, _vp, _sz, _vp]),
     'ampconv_sbm_count': (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, ctypes.c_uint64, _vp, _vp, _vp]),
     'ampconv_sbm_fill': (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, ctypes.c_uint64, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    'ampconv_mfm_workspace_bytes': (_sz, [_i64, _i32, _i32]),
+    'ampconv_mfm_build': (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32, _i32,
+                                 _vp, _vp, _vp, _vp, _i32, _vp]),
+    'ampconv_mfm_token_grad': (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _sz, _i32, _vp]),
+    'ampconv_mfm_loss_fwd': (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    'ampconv_mfm_loss_bwd': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
 }
 
 _lib = None

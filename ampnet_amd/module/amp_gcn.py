@@ -49,6 +49,7 @@ from .. import _lib
 from ..conv import AMPConv
 from ..glue import ActDropout, TokenReadout
 from ..head import MAX_CLASSES, classifier_head, saint_nll_loss
+from ..masked import MaskedValueHead, masked_value_loss
 from ..norm import NormTokenReadout, TokenLayerNorm
 from .diagnostics import Diagnostics
 from .feature_tokens import FeatureTokens
@@ -77,7 +78,7 @@ class AMPGCN(Diagnostics, nn.Module):
                  num_sampled_vectors=40, output_dim=7, softmax_out=True, feat_emb_dim=99, val_emb_dim=1,
                  downsample_feature_vectors=True, average_pooling_flag=True, dropout_rate=0.1,
                  dropout_adj_rate=0.1, feature_repeats=5, seed=0, fused_glue=False, fused_head=False, layer_norm=False,
-                 storage_dtype=torch.float32, readout_token_only=False):
+                 storage_dtype=torch.float32, readout_token_only=False, masked_modelling=False):
         super().__init__()
         if readout_token_only and average_pooling_flag:
             raise ValueError('readout_token_only=True needs average_pooling_flag=False: with the token mean every token '
@@ -150,6 +151,16 @@ class AMPGCN(Diagnostics, nn.Module):
         self._sites = tuple(self._glue) if self.fused_glue else torch_sites
         if self.layer_norm:
             self._sites = (self._sites[0], self.norm1, self.norm2)
+        # masked_modelling: the masked-autoencoder parameter of the reference's model classes under its name, shape and
+        # init (gcn_one_layer.py:43-54; commented out in amp_gcn.py:60) and the value decoder of masked_feature_loss().
+        # Created behind every other sub-module: their init RNG consumption and values do not change.  Both stay fp32
+        # under bf16 storage.  Off (the default): neither exists, the reference class's state dict.
+        self.masked_modelling = bool(masked_modelling)
+        self.token_mask = None
+        if self.masked_modelling:
+            self.mask_token = nn.Parameter(torch.zeros(1, embedding_dim))
+            nn.init.normal_(self.mask_token, std=.02)
+            self.value_decoder = MaskedValueHead(embedding_dim)
 
     def _check_storage(self):
         """model.float() / model.to(torch.bfloat16) cast every parameter; the kernels behind the table, the norm sites and
@@ -173,32 +184,38 @@ class AMPGCN(Diagnostics, nn.Module):
         the table out of training."""
         return self._tokens[0].load_umap_table(x, freeze, **umap_args)
 
-    def _run(self, data, feature_indices=None, sites=None):
+    def _run(self, data, feature_indices=None, sites=None, featurise=None, readout=True):
         """The layer walk up to the token pooling: [N, embedding_dim], the input of final_linear_out.  Sets
         conv1_embedding, conv2_embedding and sampled_node_feat_indices.  sites: a dict that receives, in this order, the
-        tensors the diagnostics show -- both layer outputs, each followed by its site's activate(), and the pooled rows."""
+        tensors the diagnostics show -- both layer outputs, each followed by its site's activate(), and the pooled rows.
+        featurise: a function x -> (tokens [N, L * D], sampled indices) in place of the model's featuriser (the masked
+        tokens of masked_feature_loss); readout=False: the walk stops behind conv2 and returns its raw output."""
         self._check_storage()
         x, edge_index = data.x.to(self.device), data.edge_index.to(self.device)
         if self.training and self.dropout_adj_rate > 0:                       # dropout_adj (amp_gcn.py:241)
             keep = torch.rand(edge_index.size(1), device=edge_index.device) >= self.dropout_adj_rate
             edge_index = edge_index[:, keep]
-        if self.downsampling_vectors:
+        if featurise is not None:
+            x, sampled = featurise(x)
+        elif self.downsampling_vectors:
             x, sampled = self._tokens[0](x, feature_indices)
         else:
             x, sampled = self._tokens[0].forward_all(x, self.feature_repeats)
         self.sampled_node_feat_indices = sampled
         for site in self._glue:                                               # a plain list, not sub-modules: train() and
             site.train(self.training)                                         # eval() miss them
-        entry, between, readout = self._sites
+        entry, between, readout_site = self._sites
         self.conv1_embedding = h1 = self.conv1(entry(x), edge_index)
         if self.readout_token_only:                                           # [N, D]: token 0 is all the readout reads
             self.conv2_embedding = h2 = self.conv2.forward_token(between(h1), edge_index, 0)
         else:
             self.conv2_embedding = h2 = self.conv2(between(h1), edge_index)
-        pooled = readout(h2)
+        if not readout:
+            return h2
+        pooled = readout_site(h2)
         if sites is not None:
             act = 'LayerNorm+ReLU' if self.layer_norm else 'ReLU'
-            shown = {'AmpConv 1': h1, act + ' 1': between.activate(h1), 'AmpConv 2': h2, act + ' 2': readout.activate(h2),
+            shown = {'AmpConv 1': h1, act + ' 1': between.activate(h1), 'AmpConv 2': h2, act + ' 2': readout_site.activate(h2),
                      'Average Pooling' if self.average_pooling_flag else 'Class Token': pooled}
             sites.update((k, v.contiguous()) for k, v in shown.items())
         return pooled
@@ -229,6 +246,36 @@ class AMPGCN(Diagnostics, nn.Module):
         y = y.to(self.device)
         return saint_nll_loss(pooled, self.final_linear_out.weight, self.final_linear_out.bias, y,
                               None if node_norm is None else node_norm.to(self.device), masks, grad_mask, metrics)
+
+    def masked_feature_loss(self, data, mask_rate=0.15, mask_mode='token', feature_indices=None, token_mask=None,
+                            metrics=None):
+        """The predictive self-supervised loss (the `criterion` that experiments/predictive_ssl_AMPNet.py leaves open): a
+        share mask_rate of the tokens is hidden behind mask_token (mask_mode 'token': the whole token vector, the
+        reference's replacement at gcn_classifier.py:151; 'value': its z-scored value alone, the feature's identity kept),
+        the model runs dropout_adj -> masked tokens -> entry site -> conv1 -> between site -> conv2, and value_decoder reads
+        conv2's raw output: the mean squared error of the hidden values over the masked tokens, a 0-dim tensor on the
+        device (ampnet_amd.masked_value_loss; no readout site, no pooling, no device synchronisation behind the
+        featuriser).  token_mask [N, L] bool replays a mask instead of drawing one; metrics: a MaskedMetrics.  Sets
+        conv1_embedding, conv2_embedding and sampled_node_feat_indices as forward does, and token_mask.  Needs
+        AMPGCN(masked_modelling=True); raises with readout_token_only=True (conv2 then computes one token)."""
+        if not self.masked_modelling:
+            raise ValueError('masked_feature_loss needs AMPGCN(masked_modelling=True): the model has no mask_token and no '
+                             'value_decoder')
+        if self.readout_token_only:
+            raise ValueError('masked_feature_loss needs every token of conv2: readout_token_only=True computes one')
+        found = {}
+
+        def featurise(x):
+            repeats = None if self.downsampling_vectors else (self.feature_repeats or 1)
+            tokens, sampled, found['masked'], found['target'] = self._tokens[0].forward_masked(
+                x, feature_indices if self.downsampling_vectors else None, rate=mask_rate, mode=mask_mode,
+                mask_token=self.mask_token, masked=token_mask, full_width_repeats=repeats)
+            return tokens, sampled
+
+        h2 = self._run(data, featurise=featurise, readout=False)
+        self.token_mask = found['masked']
+        return masked_value_loss(h2, found['masked'], found['target'], self.value_decoder.weight, self.value_decoder.bias,
+                                 metrics)
 
     def forward(self, data, feature_indices=None):
         x = self._pooled(data, feature_indices)

@@ -133,6 +133,53 @@ class FeatureTokens(nn.Module):
         tokens = _BuildTokens.apply(table.contiguous(), x, mean, inv_std, idx, self.token_dtype)
         return tokens.view(x.size(0), -1), None
 
+    def forward_masked(self, x, idx=None, *, rate, mode='token', mask_token, masked=None, full_width_repeats=None):
+        """The tokens of masked feature modelling (ampnet_amd/masked.py): `forward` -- or, with full_width_repeats given,
+        `forward_all(x, full_width_repeats)` -- with a share `rate` of the tokens hidden behind `mask_token` (the reference
+        models' parameter, [1, feat_emb_dim + 1] float32): mode 'token' replaces the whole token vector
+        (gcn_classifier.py:151), 'value' its z-scored value alone.  The mask is drawn from this module's seeded stream, or
+        `masked` [N, L] bool is replayed.  Returns (tokens [N, L * D], idx [N, L] -- None at full width --, masked [N, L]
+        bool, target [N, L] float32: the z-scored value of every token).  Gradients reach the table and mask_token."""
+        from ..masked import build_masked_tokens
+        if not x.is_cuda or x.dtype != torch.float32:
+            raise ValueError('FeatureTokens needs float32 node features on the GPU (no CPU fallback)')
+        x = x.contiguous()
+        table = self.feature_embedding_table.weight
+        if full_width_repeats is not None:
+            if idx is not None:
+                raise ValueError('full-width tokens take every feature column: feature indices cannot be given')
+            reps = int(full_width_repeats) if full_width_repeats else 1
+            if reps > 1:
+                table = table.repeat(reps, 1)
+            if table.size(0) != x.size(1) or x.size(1) != self.num_sampled_vectors:
+                raise ValueError(f'full-width tokens need num_node_features * feature_repeats ({table.size(0)}) == '
+                                 f'x.shape[1] ({x.size(1)}) == num_sampled_vectors ({self.num_sampled_vectors}) '
+                                 '(torch.cat / reshape of amp_gcn.py:174-181 raise otherwise)')
+            used, sampled = torch.arange(x.size(1), dtype=torch.int32, device=x.device).repeat(x.size(0), 1), None
+        else:
+            if idx is not None:
+                idx = torch.as_tensor(idx, device=x.device)
+                if idx.dim() != 2 or idx.size(0) != x.size(0) or idx.numel() == 0 or idx.is_floating_point():
+                    raise ValueError(f'feature indices must be integers [{x.size(0)}, num_sampled_vectors], got '
+                                     f'{idx.dtype} {tuple(idx.shape)}')
+                lo, hi = int(idx.min()), int(idx.max())
+                width = min(x.size(1), table.size(0))
+                if lo < 0 or hi >= width:
+                    raise ValueError(f'feature indices outside [0, {width}): min {lo}, max {hi}')
+                idx = idx.to(torch.int32)
+            else:
+                idx, empty = self.sample(x)
+                if int(empty.item()):
+                    raise ValueError('a node has no present (non-zero) feature to sample from '
+                                     '(np.random.choice raises in the reference, amp_gcn.py:135)')
+            used = sampled = idx.contiguous()
+        self._calls += 1
+        seed = (self._seed * 1000003 + self._calls) & (2 ** 64 - 1)
+        mean, inv_std = self.zscore_stats(x)
+        tokens, mask, target = build_masked_tokens(table, mask_token, x, mean, inv_std, used, seed=seed, rate=rate, mode=mode,
+                                                   masked=masked, dtype=self.token_dtype)
+        return tokens.view(x.size(0), -1), sampled, mask.view(torch.bool), target
+
     def forward(self, x, idx=None):
         if not x.is_cuda or x.dtype != torch.float32:
             raise ValueError('FeatureTokens needs float32 node features on the GPU (no CPU fallback)')

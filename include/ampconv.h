@@ -1458,6 +1458,82 @@ int ampconv_sbm_fill(const int64_t *sizes, int K, const double *P, const double 
                      uint64_t seed, const int64_t *off, const int64_t *moff, int64_t mirror_base, int64_t *row, int64_t *col,
                      int64_t E, void *stream);
 
+/* ---- MASKED FEATURE MODELLING (csrc/mfm.hip; pure additions, the ABI number stays 111) -------------------------------
+ * The training signal of the reference's predictive_ssl_AMPNet.py, which stops at `criterion = None`: some tokens of the
+ * featuriser are hidden behind a learned mask token (the masked-autoencoder `mask_token` of every reference model class,
+ * gcn_one_layer.py:43-54; the replacement loop of gcn_classifier.py:138-151) and a linear decoder behind the last AMPConv
+ * layer is asked for their z-scored values back: the mean squared residual over the masked tokens.  One pass per
+ * direction that reads the masked rows only.  N nodes, L tokens per node, T = N L tokens, t = n L + l.
+ *
+ * THE TOKEN MASK (a contract, like THE SAMPLING STREAM: tests rebuild it on the host, tests/mfm_reference.py).  With the
+ * library's stream draw(seed, a, b) = splitmix64(seed ^ splitmix64(a * 0x100000001B3 + b)) (uint64, wrapping):
+ *   token (n, l) is MASKED iff idx[n, l] >= 0 and (uint32)(draw(seed, n, l) >> 48) < threshold.
+ * The caller passes threshold = round(rate * 65536), 0 <= threshold <= 65536 (anything else: AMPCONV_E_BADARG); the
+ * comparison is a 32-bit one, so 65536 masks every valid token and 0 none.  The mask depends on (seed, n, l) only: not on
+ * the dtype, the row width or the launch shape.
+ *
+ * ampconv_mfm_build: ampconv_feat_build_as with the masking fused in.  x, mean, inv_std, idx, table, N, F, L, De, out,
+ *   dtype as there (out [N, L, De + 1] in `dtype`), and: mask_token [De + 1] fp32; seed, threshold: THE TOKEN MASK;
+ *   masked_in [N, L] bytes or NULL -- not NULL: that mask is REPLAYED (a token is masked iff masked_in[t] != 0 and
+ *   idx[t] >= 0) and seed, threshold are not used (threshold is still checked).  Outputs besides `out`:
+ *     masked [N, L] uint8: 1 for a masked token, else 0 -- the mask that was used;
+ *     target [N, L] fp32: z = (x[n, idx] - mean[idx]) * inv_std[idx] of EVERY token, masked or not, the fp32 value that
+ *                         feat_build puts into the value slot before any rounding to `dtype`; 0 where idx == -1.
+ *   mode AMPCONV_MFM_TOKEN: a masked token is mask_token as a whole, out[t, c] = mask_token[c] for c in [0, De]
+ *                           (gcn_classifier.py:151).
+ *   mode AMPCONV_MFM_VALUE: a masked token keeps out[t, :De] = table[idx[t]] and gets out[t, De] = mask_token[De]: the
+ *                           value is hidden, the identity of the feature is kept (with sampled tokens the only
+ *                           well-posed task: which feature a hidden token stood for is otherwise unknown).
+ *   Every element is the fp32 value rounded to nearest even to `dtype`.  An unmasked token, and a token with idx == -1
+ *   (a zero row, never masked), has the bits ampconv_feat_build_as writes; with threshold == 0 the whole of `out` has.
+ * ampconv_mfm_token_grad: dmask_token [De + 1] fp32 from dout [N, L, De + 1] (read in `dtype`, summed in fp32).  TOKEN:
+ *   dmask_token[c] = sum of dout[t, c] over the masked tokens; VALUE: component De is that sum, the others exact zeros.
+ *   Rows of unmasked tokens are not read.  The table gradient needs no call of its own: ampconv_feat_table_grad_from on
+ *   idx with the masked entries set to -1 (TOKEN), on idx as it is (VALUE).
+ * ampconv_mfm_loss_fwd: h [N, L, D] contiguous in `dtype`, masked [N, L] bytes, target [N, L] fp32, w [D] and b [1] fp32.
+ *   For each MASKED token only (masked[t] != 0):  pred = b + sum_c w[c] h[t, c],  r = pred - target[t], fp32 arithmetic.
+ *   Rows of unmasked tokens are NOT READ (they may hold NaN).  Outputs:
+ *     resid [N, L] fp32: r for the masked tokens, exact 0 elsewhere;
+ *     state int64 [2], overwritten: this call's own sums, state[0] = sum over the masked tokens of
+ *           rint(r * r * 2^AMPCONV_MFM_LOSS_SHIFT), the product of the fp32 r taken in fp64 (exact), state[1] = their number;
+ *     sums  int64 [2] or NULL (not wanted): state is ADDED to it -- the caller zeroes it (a running buffer over many calls);
+ *     *loss fp32 on the device = state[0] / 2^SHIFT / max(state[1], 1): the mean squared residual, 0 without masked tokens.
+ *   The sums are 64-bit integer atomics (the fixed point of AMPCONV_HEAD_LOSS_SHIFT): independent of the order, so
+ *   bitwise reproducible; per-term error <= 2^-33; exact while the sum of squares stays below 2^31.  No host read-back.
+ * ampconv_mfm_loss_bwd: h, masked, w as above, resid and state as loss_fwd left them, *g the upstream gradient of *loss,
+ *   read ON THE DEVICE like the count state[1]:  c = 2 * *g / max(state[1], 1),
+ *     dh[t, :] = c * resid[t] * w for the masked tokens, exact zeros for all others: the whole [N, L, D] is written, in
+ *                `dtype` (rounded to nearest even); NULL: not wanted;
+ *     dw[c] = sum_t c * resid[t] * h[t, c],  db[0] = sum_t c * resid[t]   over the masked tokens (rows of the others are
+ *                not read), fp32.
+ *   Without masked tokens dh, dw and db are exact zeros and nothing is NaN.
+ * DETERMINISM.  Every output has the same bits on every launch.  dw, db and dmask_token: a fixed-order two-stage
+ * reduction -- per workgroup the tokens in a fixed order, the workgroup's partial row in `workspace`
+ * (ampconv_mfm_workspace_bytes(N, L, D), D = De + 1 for token_grad; need not be zeroed), the rows added in workgroup order
+ * by a second kernel.  No floating-point atomics in any of these kernels.
+ * ACCESS.  A token row sits in the registers of a group of 4..64 lanes.  h, dh and dout are read and written in 16-byte
+ * pieces where they and w are 16-byte aligned and D is a whole number of pieces (bf16: 8-byte pieces where those hold
+ * for 8 bytes and D % 4 == 0), element by element otherwise (the XOR toy's D = 3).  The build moves one element per lane
+ * (a table row of De floats starts on no 16-byte boundary).
+ * ERRORS, nothing launched: a negative size, L < 1, D < 1, F < 1, De < 0, N L D beyond int64, an unknown mode, a threshold
+ * above 65536 or a missing pointer: AMPCONV_E_BADARG; a dtype other than AMPCONV_F32 / AMPCONV_BF16: AMPCONV_E_DTYPE; a
+ * workspace shorter than ampconv_mfm_workspace_bytes: AMPCONV_E_WORKSPACE.  N == 0 succeeds (data pointers may be NULL):
+ * the loss is 0, state zeros, dw, db and dmask_token zeros.  */
+enum { AMPCONV_MFM_TOKEN = 0, AMPCONV_MFM_VALUE = 1 };
+#define AMPCONV_MFM_LOSS_SHIFT 32
+size_t ampconv_mfm_workspace_bytes(int64_t N, int L, int D);
+int ampconv_mfm_build(const float *x, const float *mean, const float *inv_std, const int32_t *idx, const float *table,
+                      int64_t N, int F, int L, int De, const float *mask_token, uint64_t seed, uint32_t threshold, int mode,
+                      const uint8_t *masked_in, void *out, uint8_t *masked, float *target, int dtype, void *stream);
+int ampconv_mfm_token_grad(const void *dout, const uint8_t *masked, int64_t N, int L, int De, int mode, float *dmask_token,
+                           void *workspace, size_t workspace_bytes, int dtype, void *stream);
+int ampconv_mfm_loss_fwd(const void *h, const uint8_t *masked, const float *target, const float *w, const float *b,
+                         int64_t N, int L, int D, float *resid, int64_t *sums, int64_t *state, float *loss, int dtype,
+                         void *stream);
+int ampconv_mfm_loss_bwd(const void *h, const uint8_t *masked, const float *resid, const float *w, const int64_t *state,
+                         const float *g, int64_t N, int L, int D, void *dh, float *dw, float *db, void *workspace,
+                         size_t workspace_bytes, int dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
